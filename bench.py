@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X Kaiju classification path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline workload, warms up, times K steps and prints ONE JSON line (`value`, `ms_per_step`, ...).
+Everything below that goes beyond the headline figure - the further legs, `roofline`, `cpu_baseline` and `parity` - runs
+only with --full.  --dump-outputs DIR writes the 16-byte records of the last timed step (a fixed, seeded sample of at most
+2^20 reads: fields lca, best and info as float64, and their read indices) as DIR/<name>.npy.
 
 One *step* is one pass of the hot path (six-frame translation -> SEG -> MEM search on the protein
 FM-index -> locate / taxon ids -> LCA, kaiju_gpu_classify_batch_device + kaiju_gpu_lca_batch_device)
@@ -239,6 +244,27 @@ def reads_of_range(db, lo, hi, paired, seed):
     return np.ascontiguousarray(np.concatenate(parts, axis=0))
 
 
+def host_threads():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it"""
+    n = len(os.sched_getaffinity(0))
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(cap)) if cap.isdigit() and int(cap) > 0 else n)
+
+
+DUMP_READS = 1 << 20          # --dump-outputs: 4 float64 arrays of at most this many reads (32 MB)
+
+
+def dump_outputs(leg, d):
+    """what a caller of the timed path receives - one 16-byte record (kaiju_gpu_compact) per read - of the leg's last timed
+    step, as float64 arrays: all reads, or a fixed, seeded sample of DUMP_READS of them in read order"""
+    rec = np.frombuffer(leg.timed_compact.cpu().numpy(), dtype=api.COMPACT_DTYPE)
+    idx = np.arange(leg.n) if leg.n <= DUMP_READS else np.sort(np.random.default_rng(20261016).choice(leg.n, DUMP_READS, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "read_index.npy"), idx.astype(np.float64))
+    for f in ("lca", "best", "info"):
+        np.save(os.path.join(d, f"{f}.npy"), rec[f][idx].astype(np.float64))
+
+
 def vm_hwm_bytes():
     try:
         with open("/proc/self/status") as f:
@@ -359,7 +385,7 @@ class Leg:
         g.wait()
         self.gathered += g.bytes_gathered
 
-    def run(self, steps, warmup):
+    def run(self, steps, warmup, full=True):
         torch = self.torch
         for _ in range(warmup):
             self.step(False)
@@ -375,6 +401,11 @@ class Leg:
         self.elapsed = kdist.max_over_ranks(mine, device=self.dev)
         self.steps = steps
         self.gathered_timed = self.gathered
+        # the records the last timed step wrote: the parity leg and --dump-outputs read this snapshot, never what the
+        # passes below leave in d_compact
+        self.timed_compact = self.d_compact.clone()
+        if not full:
+            return self
         # one more, untimed, pass with the chunks strictly one after the other: kernel durations free of the other
         # chunk's kernels (what rocprofv3 --kernel-trace shows for `--contexts 1`)
         live = (list(self.kern_ms), dict(self.stage_ms))
@@ -387,9 +418,6 @@ class Leg:
         self.excl_kern = [min(a, b) for a, b in zip(passes[0][0], passes[1][0])]
         self.excl_stage = {k: min(passes[0][1][k], passes[1][1][k]) for k in passes[0][1]}
         self.kern_ms, self.stage_ms = live
-        # the records the TIMED kernels wrote (the pass above runs exactly the launches of a timed step): the parity leg
-        # reads this snapshot, never what the counting pass below leaves in d_compact
-        self.timed_compact = self.d_compact.clone()
         # accounting: the counting instantiation of the lane on the first chunk (untimed)
         c = self.clfs[0]
         c.count_ops(True)
@@ -407,6 +435,12 @@ class Leg:
     def result(self, world, ref_ops, traffic, nseq):
         tot_units = self.n * world * self.steps
         value = tot_units / self.elapsed
+        out = {"value": value, "unit": "pairs/s" if self.paired else "reads/s", "steps": self.steps,
+               "ms_per_step": self.elapsed / self.steps * 1e3, "units_per_gpu_per_step": self.n,
+               "contexts_in_flight": self.nctx, "chunk": self.chunk,
+               "overflow_retries_per_step": self.retries / max(self.steps, 1)}
+        if not hasattr(self, "op_counts"):            # (run(.., full=False): no untimed passes, no roofline)
+            return out
         excl_ms = sum(ms for ms, _ in self.excl_kern) / max(len(self.excl_kern), 1)
         live_ms = sum(ms for ms, _ in self.kern_ms) / max(len(self.kern_ms), 1)
         per_launch = float(sum(m for _, m in self.excl_kern)) / max(len(self.excl_kern), 1)
@@ -438,10 +472,7 @@ class Leg:
                                  "note": "SURVEY.md 8(d): bytes the REFERENCE's algorithm would touch for this work (128 B per "
                                          "UpdateSI ...); the k-mer table replaces most of those steps, so this is a rate of "
                                          "work, not traffic, and is not compared with the HBM peak"}
-        return {"value": value, "unit": "pairs/s" if self.paired else "reads/s", "steps": self.steps,
-                "ms_per_step": self.elapsed / self.steps * 1e3, "units_per_gpu_per_step": self.n,
-                "contexts_in_flight": self.nctx, "chunk": self.chunk,
-                "overflow_retries_per_step": self.retries / max(self.steps, 1), "roofline": roof}
+        return {**out, "roofline": roof}
 
     def host_records(self, k):
         """finalised (classified, taxon) of the first k reads from the device's compact records"""
@@ -628,8 +659,9 @@ def summary_line(result: dict, detail_path) -> str:
                      "ranks": cfg.get("ranks"), "gather": str(cfg.get("gather") or "none")[:160], "gather_by": cfg.get("gather_by"),
                      "process_group": cfg.get("process_group"),
                      "per_rank_units_per_s": [_sig(v) for v in (cfg.get("per_rank_units_per_s") or [])][:16]}
-    out["roofline"] = {k: _sig(roof.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
-                                                      "algorithmic_bytes_per_unit", "units_per_launch", "avg_launch_ms")}
+    if roof:
+        out["roofline"] = {k: _sig(roof.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
+                                                          "algorithmic_bytes_per_unit", "units_per_launch", "avg_launch_ms")}
     st = roof.get("stage_ms_per_step_exclusive")
     if st:
         out["stage_ms"] = {k: _sig(v, 4) for k, v in st.items()}
@@ -747,6 +779,12 @@ def main():
                          "kaiju_gpu_gather_compact: librccl opened by libkaiju_gpu.so, one ncclGather per chunk, no torch in the data path)")
     ap.add_argument("--parity-sample", type=int, default=200_000,
                     help="N > 1: reads (pairs) of EVERY rank whose gathered records rank 0 compares with the reference binary")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the further legs (--legs), roofline and op counts (untimed passes), CPU baseline and "
+                         "parity with the reference binary; without it a run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the records of the headline's last timed step to DIR/<name>.npy (float64; a fixed, seeded sample of "
+                         f"at most {DUMP_READS} reads)")
     args = ap.parse_args()
 
     # ---------------- N ranks: launch them ourselves when nobody did ----------------
@@ -758,7 +796,7 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
         print("[bench] starting", args.gpus, "ranks:", " ".join(cmd), file=sys.stderr, flush=True)
-        os.execvp(cmd[0], cmd)
+        raise SystemExit(subprocess.call(cmd))        # (a fresh child: this process has already opened the GPU runtime)
 
     import torch
     if args.prepare_only:
@@ -777,7 +815,8 @@ def main():
     seg = 0 if args.no_seg else 1
     W = args.work
     os.makedirs(W, exist_ok=True)
-    legs_wanted = [x for x in args.legs.split(",") if x]
+    legs_wanted = [x for x in args.legs.split(",") if x] if args.full else []
+    threads = host_threads()
 
     # ---------------- workload (untimed) ----------------
     t0 = time.time()
@@ -790,21 +829,54 @@ def main():
     log(rank, f"database {db.nseq} seqs / {db.total_aa} aa ({time.time()-t0:.1f}s)")
     copies = max(1, args.copies)
     fmi, nodes = f"{W}/db_{args.nseq}{'' if copies == 1 else f'_x{copies}'}.fmi", f"{W}/nodes.dmp"
+
+    def build_index():
+        t1 = time.time()
+        faa = f"{W}/db_{args.nseq}.faa"
+        if not big_db:
+            synth.write_fasta(db, faa)
+        if copies == 1:
+            mkfmi.build_fmi(faa, fmi + ".tmp", threads=threads, exponent=3)
+        else:
+            mkfmi.build_fmi_replicated(faa, fmi + ".tmp", copies, threads=threads, exponent=3, copy_taxids=np.asarray(leaves, dtype=np.uint64))
+        os.replace(fmi + ".tmp", fmi)
+        if big_db:
+            os.remove(faa)
+        log(rank, f".fmi built ({time.time()-t1:.1f}s)")
+
+    index_job = None
     if rank == 0:
         synth.write_nodes_dmp(nodes, lines)
         if not os.path.exists(fmi):
-            t1 = time.time()
-            faa = f"{W}/db_{args.nseq}.faa"
-            if not big_db:
-                synth.write_fasta(db, faa)
-            if copies == 1:
-                mkfmi.build_fmi(faa, fmi + ".tmp", threads=0, exponent=3)
-            else:
-                mkfmi.build_fmi_replicated(faa, fmi + ".tmp", copies, threads=0, exponent=3, copy_taxids=np.asarray(leaves, dtype=np.uint64))
-            os.replace(fmi + ".tmp", fmi)
-            if big_db:
-                os.remove(faa)
-            log(rank, f".fmi built ({time.time()-t1:.1f}s)")
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(1)
+            index_job = pool.submit(build_index)      # (while the reads below are generated: the builder's sort is native code)
+            pool.shutdown(wait=False)
+    n = args.reads
+    Lm = 150
+    if args.strong:
+        if args.reads % world:
+            raise SystemExit(f"--strong: --reads {args.reads} is not a multiple of the {world} ranks (equal blocks: one gather size)")
+        n = args.reads // world
+
+    def make(paired, count, seed):
+        if args.strong:
+            # rank r classifies the contiguous block [r * count, (r + 1) * count) of the one workload
+            lo, hi = kdist.shard_bounds(count * world, rank, world)
+            return reads_of_range(db, lo, hi, paired, seed * 1000)
+        if paired:
+            m1, m2 = synth.make_pairs(db, count, seed=seed + rank)
+            return np.concatenate([m1, m2], axis=1)           # pair r = mate 1 followed by mate 2 in the sequence buffer
+        return synth.make_reads(db, count, seed=seed + rank, threads=threads)
+
+    reads = None
+    if not args.prepare_only:
+        t1 = time.time()
+        reads = make(args.paired, n, 778 if args.paired else 777)
+        log(rank, f"{n} {'pairs' if args.paired else 'reads'}/GPU generated ({time.time()-t1:.1f}s)")
+    if index_job is not None:
+        index_job.result()
+    if rank == 0:
         log(rank, f"index {os.path.getsize(fmi)/1e6:.0f} MB file{'' if copies == 1 else f' ({copies} copies of every protein)'} "
                   f"({time.time()-t0:.1f}s)")
     kdist.barrier()
@@ -850,30 +922,10 @@ def main():
     if args.gather == "lib" and (world > 1 or os.environ.get("KAIJU_DIST_FORCE_INIT") == "1"):
         Leg.comm = kdist.make_comm(W, rank, world, local_rank)
         log(rank, f"gather through the library's RCCL communicator ({world} rank(s))")
-    n = args.reads
-    Lm = 150
-    if args.strong:
-        if args.reads % world:
-            raise SystemExit(f"--strong: --reads {args.reads} is not a multiple of the {world} ranks (equal blocks: one gather size)")
-        n = args.reads // world
-
-    def make(paired, count, seed):
-        if args.strong:
-            # rank r classifies the contiguous block [r * count, (r + 1) * count) of the one workload
-            lo, hi = kdist.shard_bounds(count * world, rank, world)
-            return reads_of_range(db, lo, hi, paired, seed * 1000)
-        if paired:
-            m1, m2 = synth.make_pairs(db, count, seed=seed + rank)
-            return np.concatenate([m1, m2], axis=1)           # pair r = mate 1 followed by mate 2 in the sequence buffer
-        return synth.make_reads(db, count, seed=seed + rank)
-
-    t0 = time.time()
-    reads = make(args.paired, n, 778 if args.paired else 777)
-    log(rank, f"{n} {'pairs' if args.paired else 'reads'}/GPU generated ({time.time()-t0:.1f}s), index {index.info.device_bytes/1e6:.0f} MB in HBM")
 
     def do_leg(name, mode, paired, rd, steps, warmup):
         leg = Leg(name, mode, paired, rd, Lm, index, dtax, dev, rank, world, seg, args.chunk, args.contexts)
-        leg.run(steps, warmup)
+        leg.run(steps, warmup, full=args.full)
         log(rank, f"leg {name}: {leg.n * world * steps / leg.elapsed / 1e6:.1f} M {'pairs' if paired else 'reads'}/s")
         return leg
 
@@ -886,9 +938,14 @@ def main():
         outl = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(outl, t)
         per_rank = [float(x.item()) for x in outl]
-    hits = np.frombuffer(head.d_out[: min(n, 1_000_000) * HIT_BYTES].cpu().numpy().tobytes(), dtype=api.HIT_DTYPE)
-    frac_hit = float((hits["n_ids"] > 0).mean())
-    del hits
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(head, args.dump_outputs)
+        log(rank, f"records of the last timed step written to {args.dump_outputs}")
+    frac_hit = None
+    if args.full:
+        hits = np.frombuffer(head.d_out[: min(n, 1_000_000) * HIT_BYTES].cpu().numpy().tobytes(), dtype=api.HIT_DTYPE)
+        frac_hit = float((hits["n_ids"] > 0).mean())
+        del hits
 
     # ---------------- further legs ----------------
     extra = {}
@@ -986,7 +1043,7 @@ def main():
     # N > 1: a sample of EVERY rank's reads and of the records its timed kernels wrote goes to rank 0, which checks each against
     # the reference binary (an N-GPU line must not state a rate with nothing looking at the gathered records)
     rank_samples = None
-    if world > 1 and not args.no_cpu_baseline and args.parity_sample > 0:
+    if world > 1 and args.full and not args.no_cpu_baseline and args.parity_sample > 0:
         k = min(args.parity_sample, n)
         rd_t = torch.from_numpy(np.ascontiguousarray(reads[:k]).reshape(-1)).to(dev)
         rec_t = head.timed_compact[: k * COMPACT_BYTES].contiguous()
@@ -998,7 +1055,7 @@ def main():
     # ---------------- accounting legs on the host: reference baseline + parity, reference op counts ----------------
     def cpu_leg(leg, rd, sample, oracle_sample, fmi=fmi, tag_suffix=""):
         out = {"ref_ops": None, "baseline": None, "parity": None}
-        if args.no_cpu_baseline or world != 1:
+        if args.no_cpu_baseline or world != 1 or not args.full:
             return out
         try:
             if not args.no_ref_ops and oracle_sample > 0:
@@ -1080,11 +1137,13 @@ def main():
                    "gather": (f"one async RCCL gather of 16-B records (device LCA of the 184-B hit records) per chunk to rank 0; "
                               f"{head.gathered_timed / max(args.steps, 1):.0f} B into rank 0 per step"
                               if world > 1 else "none (1 GPU); device LCA to 16-B records still runs"),
-                   "fraction_reads_with_hit": round(frac_hit, 4), "overflow_retries_per_step": hr["overflow_retries_per_step"],
+                   **({"fraction_reads_with_hit": round(frac_hit, 4)} if frac_hit is not None else {}),
+                   "overflow_retries_per_step": hr["overflow_retries_per_step"],
                    "design_note": "one READ per lane following the reference's sequential pruning (DESIGN.md 3.3), rank blocks "
                                   "read straight from HBM as 128-byte lines - not one fragment per lane with LDS-staged Occ blocks"},
-        "roofline": hr["roofline"],
     }
+    if "roofline" in hr:
+        result["roofline"] = hr["roofline"]
     if acc["headline"]["baseline"] is not None:
         result["cpu_baseline"] = acc["headline"]["baseline"]
     parity = {}

@@ -309,8 +309,15 @@ def write_fasta(db: SynthDB, path, width=0):
             f.write(b"\n")
 
 
-def make_reads(db: SynthDB, n, seed=777, read_len=150, frac_db=0.70, chunk=1 << 20):
-    """Return (uint8 ASCII array [n, read_len]) of synthetic reads."""
+_CODNT = np.array([[(c >> 4) & 3, (c >> 2) & 3, c & 3] for c in range(64)], dtype=np.uint8)   # codon index -> 3 nt codes
+_CODTAB8 = _CODTAB.astype(np.uint8).reshape(-1)
+
+
+def make_reads(db: SynthDB, n, seed=777, read_len=150, frac_db=0.70, chunk=1 << 20, threads=1):
+    """Return (uint8 ASCII array [n, read_len]) of synthetic reads.
+
+    The random draws of every chunk are taken in one fixed order on the calling thread; what is computed from them runs on
+    up to `threads` worker threads, so the reads do not depend on `threads`."""
     rng = np.random.default_rng(seed)
     naa = read_len // 3 + 1           # 51-aa window for 150 nt
     lens = np.diff(db.offsets)
@@ -318,26 +325,56 @@ def make_reads(db: SynthDB, n, seed=777, read_len=150, frac_db=0.70, chunk=1 << 
     nt = np.frombuffer(_NT.encode(), dtype=np.uint8)
     comp = np.array([3, 2, 1, 0], dtype=np.uint8)
     out = np.empty((n, read_len), dtype=np.uint8)
-    for lo in range(0, n, chunk):
-        m = min(chunk, n - lo)
-        seq = elig[rng.integers(0, len(elig), size=m)]
-        start = db.offsets[seq] + (rng.random(m) * (lens[seq] - naa + 1)).astype(np.int64)
+
+    def fill(lo, m, seq, u_start, u_pick, off, subs, rc, rnd, rnd_reads):
+        start = db.offsets[seq] + (u_start * (lens[seq] - naa + 1)).astype(np.int64)
         win = db.codes[start[:, None] + np.arange(naa)[None, :]]            # [m, naa]
-        pick = (rng.random((m, naa)) * _NSYN[win]).astype(np.int64)
-        cod = _CODTAB[win, pick]                                            # codon index 0..63
-        nts = np.stack([(cod >> 4) & 3, (cod >> 2) & 3, cod & 3], axis=2).reshape(m, naa * 3)
-        off = rng.integers(0, 3, size=m)
-        reads = nts[np.arange(m)[:, None], off[:, None] + np.arange(read_len)[None, :]].astype(np.uint8)
-        nsub = rng.choice(np.array([0, 0, 1, 3, 8]), size=m)
-        for k in range(8):
-            sel = np.nonzero(nsub > k)[0]
-            pos = rng.integers(0, read_len, size=len(sel))
-            reads[sel, pos] = rng.integers(0, 4, size=len(sel), dtype=np.uint8)
-        rc = rng.random(m) < 0.5
+        pick = (u_pick * _NSYN[win]).astype(np.intp)
+        cod = _CODTAB8[win.astype(np.intp) * 6 + pick]                      # codon index 0..63
+        nts = _CODNT[cod].reshape(m, naa * 3)
+        reads = np.empty((m, read_len), dtype=np.uint8)
+        for o in range(3):                                                  # frame offset 0..2
+            sel = off == o
+            reads[sel] = nts[sel, o:o + read_len]
+        for sel, pos, val in subs:
+            reads[sel, pos] = val
         reads[rc] = comp[reads[rc][:, ::-1]]
-        rnd = rng.random(m) >= frac_db
-        reads[rnd] = rng.integers(0, 4, size=(int(rnd.sum()), read_len), dtype=np.uint8)
+        reads[rnd] = rnd_reads
         out[lo:lo + m] = nt[reads]
+
+    pool = None
+    if threads > 1 and n > chunk:
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(threads)
+    pending = []
+    try:
+        for lo in range(0, n, chunk):
+            m = min(chunk, n - lo)
+            seq = elig[rng.integers(0, len(elig), size=m)]
+            u_start = rng.random(m)
+            u_pick = rng.random((m, naa))
+            off = rng.integers(0, 3, size=m)
+            nsub = rng.choice(np.array([0, 0, 1, 3, 8]), size=m)
+            subs = []
+            for k in range(8):
+                sel = np.nonzero(nsub > k)[0]
+                pos = rng.integers(0, read_len, size=len(sel))
+                subs.append((sel, pos, rng.integers(0, 4, size=len(sel), dtype=np.uint8)))
+            rc = rng.random(m) < 0.5
+            rnd = rng.random(m) >= frac_db
+            rnd_reads = rng.integers(0, 4, size=(int(rnd.sum()), read_len), dtype=np.uint8)
+            args = (lo, m, seq, u_start, u_pick, off, subs, rc, rnd, rnd_reads)
+            if pool is None:
+                fill(*args)
+                continue
+            if len(pending) >= threads:          # (bounds the draws held in memory: about 0.5 GB per chunk in flight)
+                pending.pop(0).result()
+            pending.append(pool.submit(fill, *args))
+        for f in pending:
+            f.result()
+    finally:
+        if pool is not None:
+            pool.shutdown()
     return out
 
 

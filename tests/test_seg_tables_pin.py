@@ -1,16 +1,15 @@
 """The ln(n!) table of SEG (blast_seg.c:52-1308, 10 001 entries printed with six decimals) is DERIVED - from lgamma, rounded to
 six decimals - in the product (kaiju_amd/csrc/host_tables.cpp: build_seg_tables) and in the oracle (oracle/kaiju_oracle.c:
-init_lnfact) alike: a shared assumption.  Where /root/reference exists the printed table is parsed and compared entry by
-entry, bit for bit, with both; everywhere the two derivations are compared with each other."""
+init_lnfact) alike: a shared assumption.  The printed table, parsed into tests/golden/seg_lnfact.npy (make_golden_lnfact.py),
+is compared entry by entry, bit for bit, with both, and the two derivations with each other."""
 import ctypes as C
 import os
-import re
 
-import pytest
+import numpy as np
 
 import pyoracle as po
 
-BLAST_SEG = "/root/reference/src/include/ncbi-blast+/algo/blast/core/blast_seg.c"
+PRINTED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seg_lnfact.npy")
 
 
 def _tables(emu, golden):
@@ -35,12 +34,7 @@ def test_product_and_oracle_derive_the_same_table(emu, golden):
 
 
 def test_table_equals_the_one_printed_in_blast_seg_c(emu, golden):
-    if not os.path.exists(BLAST_SEG):
-        pytest.skip("the reference's sources are not on this machine")
-    text = open(BLAST_SEG).read()
-    body = text[text.index("double lnfact[]"):]
-    body = body[body.index("{") + 1: body.index("};")]
-    printed = [float(x) for x in re.findall(r"-?\d+\.\d+", body)]
+    printed = np.load(PRINTED).tolist()
     product, oracle = _tables(emu, golden)
     assert len(printed) == 10001
     assert printed == product and printed == oracle

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the hostile legs of bench.py (and the headline, for the i.i.d. side) with this library and with KAIJU_AB_LIB
 O=${1:-gpurun_out/hard_ab}; mkdir -p $O
-ARGS="--legs hard --steps 3 --leg-steps 3 --no-cpu-baseline"
+ARGS="--full --legs hard --steps 3 --leg-steps 3 --no-cpu-baseline"
 timeout 900 python bench.py $ARGS > $O/bench_new.json 2> $O/bench_new.err; echo "new rc=$?"
 OLD=${KAIJU_AB_LIB:-kaiju_amd/variants/libkaiju_gpu_base.so}
 [ -f $OLD ] && { KAIJU_GPU_LIB=$OLD timeout 900 python bench.py $ARGS > $O/bench_old.json 2> $O/bench_old.err; echo "old rc=$?"; }

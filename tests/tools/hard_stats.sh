@@ -1,8 +1,9 @@
 #!/bin/bash
 # rocprofv3 kernel summary of the hostile legs (bench.py --legs hard): which kernels the post-search bucket consists of there
 O=${1:-gpurun_out/hard_stats}; mkdir -p $O
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/st -o s -- python $GRAFT_REPO_ROOT/bench.py --legs hard --steps 1 --warmup 0 --leg-steps 4 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench.json 2> $GRAFT_REPO_ROOT/$O/bench.err
-cd $GRAFT_REPO_ROOT; cp $O/st/s_kernel_stats.csv $O/kernel_stats_hard.csv 2>/dev/null; cp $O/st/s_kernel_trace.csv $O/kernel_trace_hard.csv 2>/dev/null; rm -rf $O/st
+R=$(cd "$(dirname "$0")/../.." && pwd)
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/st -o s -- python $R/bench.py --full --legs hard --steps 1 --warmup 0 --leg-steps 4 --no-cpu-baseline > $R/$O/bench.json 2> $R/$O/bench.err
+cd $R; cp $O/st/s_kernel_stats.csv $O/kernel_stats_hard.csv 2>/dev/null; cp $O/st/s_kernel_trace.csv $O/kernel_trace_hard.csv 2>/dev/null; rm -rf $O/st
 python - <<PY
 import csv, collections
 # per kernel: the launches that belong to the hard legs = those after the hard index was built (the last k_suffix_walk)

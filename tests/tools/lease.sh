@@ -4,7 +4,7 @@
 # Tasks (each under its own timeout; a failing task does not stop the following ones):
 #   suite            pytest -m gpu (full GPU suite)                                   -> gpu_tests.log
 #   smoke            __graft_entry__.smoke()                                          -> smoke.log
-#   bench            python bench.py (default line: headline + legs + CPU baseline)   -> bench_n1.json / .err
+#   bench            python bench.py --full (headline + legs + CPU baseline)          -> bench_n1.json / .err
 #   bench:<args>     python bench.py <args> ("," stands for a blank)                  -> bench_<n>.json / .err
 #   stats            rocprofv3 --kernel-trace --stats of the headline leg, its launches   -> kernel_stats.csv
 #                    (5 M reads each) one after the other: --contexts 1 --chunk 5000000
@@ -28,7 +28,7 @@ for task in "$@"; do
     smoke)
       timeout 600 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; echo "[lease] smoke rc=$?"; tail -3 $O/smoke.log ;;
     bench)
-      timeout 1500 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "[lease] bench rc=$?"; tail -6 $O/bench_n1.err ;;
+      timeout 1500 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "[lease] bench rc=$?"; tail -6 $O/bench_n1.err ;;
     bench:*)
       args=$(echo "${task#bench:}" | tr ',' ' ')
       timeout 2400 python bench.py $args > $O/bench_$n.json 2> $O/bench_$n.err; echo "[lease] bench $args rc=$?"; tail -6 $O/bench_$n.err ;;
@@ -50,7 +50,7 @@ for task in "$@"; do
       W=/dev/shm/kaiju_big_$task; mkdir -p $W
       NSEQ=14300001; ARGS="--copies 7 --paired --reads 5000000 --steps 10 --legs greedy --leg-steps 2 --cpu-sample 200000 --cpu-sample-legs 100000"
       # the bench runs in a process group of its own, so that the watchdog can end exactly that group
-      setsid bash -c "KAIJU_GPU_LOAD_TIMES=1 exec timeout ${LEASE_BIG_TIMEOUT:-1700} python bench.py --work $W --nseq $NSEQ --image --warmup 1 --no-ref-ops $ARGS > $O/bench_$task.json 2> $O/bench_$task.err" &
+      setsid bash -c "KAIJU_GPU_LOAD_TIMES=1 exec timeout ${LEASE_BIG_TIMEOUT:-1700} python bench.py --full --work $W --nseq $NSEQ --image --warmup 1 --no-ref-ops $ARGS > $O/bench_$task.json 2> $O/bench_$task.err" &
       BP=$!
       ( while sleep 2; do
           kill -0 $BP 2>/dev/null || break
@@ -95,7 +95,7 @@ for task in "$@"; do
       guarded $O/prepare_$task.log $O/prepare_$task.err timeout 1500 python bench.py --work $W --nseq $NSEQ --copies $COPIES --prepare-only
       echo "[lease] prepare rc=$? ($(( $(date +%s) - t1 )) s)"; grep -v "kaiju mkfmi\]" $O/prepare_$task.err | tail -5
       ls -la $W > $O/files_$task.txt; df -h /dev/shm >> $O/files_$task.txt; free -g >> $O/files_$task.txt
-      KAIJU_GPU_LOAD_TIMES=1 guarded $O/bench_$task.json $O/bench_$task.err timeout ${LEASE_BIG_TIMEOUT:-1500} python bench.py --work $W --nseq $NSEQ --warmup 1 --no-ref-ops $ARGS
+      KAIJU_GPU_LOAD_TIMES=1 guarded $O/bench_$task.json $O/bench_$task.err timeout ${LEASE_BIG_TIMEOUT:-1500} python bench.py --full --work $W --nseq $NSEQ --warmup 1 --no-ref-ops $ARGS
       echo "[lease] $task rc=$?"; grep -v "^\[kaiju_gpu pack\]" $O/bench_$task.err | tail -40
       if [ -d $W ]; then
         ( cd /tmp && KAIJU_GPU_LOAD_TIMES=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats_$task -o s -- python $GRAFT_REPO_ROOT/bench.py --work $W --nseq $NSEQ --no-cpu-baseline --legs "" --steps 3 --warmup 1 --copies $COPIES --paired --reads 5000000 > $GRAFT_REPO_ROOT/$O/bench_${task}_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/bench_${task}_under_rocprof.err )

@@ -21,7 +21,7 @@ for ctrs in \
   # (PMC_PASSES="1 2": only those counter groups - the request counts the traffic figure is made of)
   if [ -n "$PMC_PASSES" ]; then case " $PMC_PASSES " in *" $i "*) ;; *) continue ;; esac; fi
   timeout 600 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $OUT/pass$i -o p -- \
-    env KAIJU_BENCH_SERIAL=1 python $R/bench.py ${PMC_BENCH_ARGS:---contexts 1} --steps 1 --warmup 0 --no-cpu-baseline --legs greedy,paired > $OUT/pass$i.json 2> $OUT/pass$i.log
+    env KAIJU_BENCH_SERIAL=1 python $R/bench.py --full ${PMC_BENCH_ARGS:---contexts 1} --steps 1 --warmup 0 --no-cpu-baseline --legs greedy,paired > $OUT/pass$i.json 2> $OUT/pass$i.log
   echo "pass $i rc=$? : $ctrs"
   rm -f $OUT/pass$i/p_agent_info.csv
 done

@@ -15,7 +15,7 @@ for leg in $LEGS; do
     i=$((i+1))
     mkdir -p $OUT/$leg
     timeout 900 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $OUT/$leg/pass$i -o p -- \
-      python $R/bench.py --reads 2000000 --contexts 1 --steps 1 --warmup 0 --leg-steps 1 --no-cpu-baseline --no-ref-ops --parity-sample 0 --legs $leg \
+      python $R/bench.py --full --reads 2000000 --contexts 1 --steps 1 --warmup 0 --leg-steps 1 --no-cpu-baseline --no-ref-ops --parity-sample 0 --legs $leg \
       > $OUT/$leg/pass$i.json 2> $OUT/$leg/pass$i.log
     echo "$leg pass $i rc=$? : $ctrs"
     rm -f $OUT/$leg/pass$i/p_agent_info.csv

@@ -5,7 +5,7 @@
 O=${1:-gpurun_out/wide_text}; mkdir -p $O
 ( time timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "text_positions_of_an_index_with_64_bit_rows or wide_index_path" ) > $O/tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/tests.log
 W=/dev/shm/kjw; mkdir -p $W
-ARGS="--work $W --nseq 15500001 --image --reads 3000000 --steps 3 --warmup 1 --leg-steps 2 --no-ref-ops"
+ARGS="--full --work $W --nseq 15500001 --image --reads 3000000 --steps 3 --warmup 1 --leg-steps 2 --no-ref-ops"
 ( time KAIJU_GPU_LOAD_TIMES=1 timeout 1500 python bench.py $ARGS --legs greedy --cpu-sample 200000 --cpu-sample-legs 100000 ) > $O/bench_tv0.json 2> $O/bench_tv0.err; echo "tv0 rc=$?"
 grep "leg \|built\|index in HBM\|text \|HBM:" $O/bench_tv0.err
 ( time KAIJU_GPU_LOAD_TIMES=1 KAIJU_GPU_TV_SHIFT=1 timeout 900 python bench.py $ARGS --legs none --no-cpu-baseline ) > $O/bench_tv1.json 2> $O/bench_tv1.err; echo "tv1 rc=$?"; grep "text \|HBM:" $O/bench_tv1.err

@@ -5,7 +5,7 @@
 O=${1:-gpurun_out/wide_text2}; mkdir -p $O
 R=$(cd "$(dirname "$0")/../.." && pwd); V=$R/kaiju_amd/variants
 W=/dev/shm/kjw; mkdir -p $W
-ARGS="--work $W --nseq 15500001 --reads 3000000 --steps 3 --warmup 1 --legs none --no-cpu-baseline --no-ref-ops"
+ARGS="--full --work $W --nseq 15500001 --reads 3000000 --steps 3 --warmup 1 --legs none --no-cpu-baseline --no-ref-ops"
 run() { tag=$1; extra=$2; shift 2; ( time env KAIJU_GPU_LOAD_TIMES=1 "$@" timeout 900 python bench.py $ARGS $extra ) > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "$tag rc=$?"; }
 run head_fmi "" KAIJU_GPU_LIB=$V/libkaiju_gpu_head.so
 grep "built" $O/bench_head_fmi.err
