@@ -4,6 +4,7 @@
 //   k_fragments  one lane per read: six-frame translation, fragment list in queue order,
 //                eager SEG split for MEM (stage 1, kj_core.h:build_fragments)
 //   k_fragments_fast  the same for mates up to 191 nt; k_trigcheck / k_segflag / k_seg / k_seg_apply*: SEG
+//   k_fragments_team  the fast stage 1 without SEG trigger detection, 16 lanes per read (mates up to 191 nt)
 //   k_mem        persistent lanes, one read at a time per lane: MEM search (+ locate for reads with many longest matches)
 //   k_mem_locate one lane per read: the ids of the reads whose one or two longest matches k_mem left in the hit record
 //   k_greedy2    persistent lanes: Greedy search (priority queue, substitutions) + locate
@@ -109,6 +110,31 @@ k_fragments_fast(const Stage1Tables *__restrict__ g_t, Params p, Batch b, SegQue
   ln.cnt = s_cnt + (TRIG ? threadIdx.x * kS1CntStride : 0);
   ln.tsbuf = nullptr;                                  // (the scan of whole strings takes its residues from registers)
   build_fragments_fast<TRIG, UNITS>(s_t, p, b, sq, r, &e, ln);
+  if (e) atomicOr(err, e);
+}
+
+// Stage 1, team path (kj_core.h: build_fragments_team): the non-TRIG fast stage 1 of mates up to kS1MaxLen nucleotides, a team
+// of 16 lanes per read, 16 reads per block.  LDS: the tables once per block and 640 bytes per team (strings of the mate at hand,
+// masks, fragment list).  Single reads only: on 2 x 150-bp pairs it lost 4 % to k_fragments_fast<false>.
+// KAIJU_GPU_STAGE1=lane: k_fragments_fast<false> for single reads too (A/B measurements).
+constexpr int kS1TeamBlock = 256;
+constexpr int kS1TeamsPerBlock = kS1TeamBlock / (int)kS1TeamLanes;
+__global__ void __launch_bounds__(kS1TeamBlock)
+k_fragments_team(const Stage1Tables *__restrict__ g_t, Params p, Batch b, uint32_t *err) {
+  __shared__ __attribute__((aligned(16))) Stage1Tables s_t;
+  __shared__ __attribute__((aligned(16))) S1TeamLds s_team[kS1TeamsPerBlock];
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(g_t);
+    uint4 *dst = reinterpret_cast<uint4 *>(&s_t);
+    for (uint32_t i = threadIdx.x; i < sizeof(Stage1Tables) / 16; i += kS1TeamBlock) dst[i] = src[i];
+    __syncthreads();
+  }
+  const uint32_t team = threadIdx.x / kS1TeamLanes;
+  const uint32_t r = blockIdx.x * kS1TeamsPerBlock + team;
+  if (r >= b.n_reads) return;
+  uint32_t e = 0;
+  S1TeamDev tm{&s_team[team], threadIdx.x % kS1TeamLanes};
+  build_fragments_team(s_t, p, b, r, &e, tm);
   if (e) atomicOr(err, e);
 }
 
@@ -1893,6 +1919,7 @@ struct kaiju_gpu_ctx {
   bool mem_v1 = false;             // KAIJU_GPU_MEM_LANE=v1 (read once, at context creation)
   bool verbose_v1 = false;         // KAIJU_GPU_VERBOSE_LANE=v1: -v from the first-generation lanes (until round 6 the only way; A/B)
   bool stage1_old = false;         // KAIJU_GPU_STAGE1=old: build_fragments for every read length (A/B measurements)
+  bool stage1_lane = false;        // KAIJU_GPU_STAGE1=lane: k_fragments_fast<false> where k_fragments_team would run
   bool lazy_seg = true;            // KAIJU_GPU_LAZY_SEG=0: SEG pass over every flagged fragment in MEM mode too
   DevBuf seglist, loc_list, todo_list;
   int seg_team = 64;               // KAIJU_GPU_SEG_TEAM: lanes per fragment of the SEG pass (64 = one wavefront per fragment, k_seg; 8, 16, 32: k_seg_teams, slower - DESIGN.md 6b)
@@ -1968,7 +1995,7 @@ extern "C" int kaiju_gpu_create(kaiju_gpu_ctx **out, const kaiju_gpu_index *ix, 
   if (const char *e = getenv("KAIJU_GPU_MEM_LANE")) c->mem_v1 = !strcmp(e, "v1");
   if (const char *e = getenv("KAIJU_GPU_VERBOSE_LANE")) c->verbose_v1 = !strcmp(e, "v1");
   c->dump_frags = getenv("KAIJU_GPU_DUMP_FRAGS");
-  if (const char *e = getenv("KAIJU_GPU_STAGE1")) c->stage1_old = !strcmp(e, "old");
+  if (const char *e = getenv("KAIJU_GPU_STAGE1")) { c->stage1_old = !strcmp(e, "old"); c->stage1_lane = !strcmp(e, "lane"); }
   if (const char *e = getenv("KAIJU_GPU_LAZY_SEG")) c->lazy_seg = atoi(e) != 0;
   if (const char *e = getenv("KAIJU_GPU_FUSED_POST")) c->fused_post = atoi(e) != 0;
   if (const char *e = getenv("KAIJU_GPU_SEG_TEAM")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 32 || v == 64) c->seg_team = v; }
@@ -2141,6 +2168,9 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
       hipLaunchKernelGGL((k_fragments_fast<false, kS1UnitsLong>), dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
     else if (fast1 && trig1)
       hipLaunchKernelGGL(k_fragments_fast<true>, dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
+    else if (fast1 && !c->stage1_lane && !paired)     // (pairs: the team kernel was slower)
+      hipLaunchKernelGGL(k_fragments_team, dim3((unsigned)((n + kS1TeamsPerBlock - 1) / kS1TeamsPerBlock)), dim3(kS1TeamBlock), 0, s,
+                         ix->d_s1, p, b, cnt + 3);
     else if (fast1)
       hipLaunchKernelGGL(k_fragments_fast<false>, dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
     else

@@ -1869,6 +1869,250 @@ KJ_HD void build_fragments_fast(const Stage1Tables &t, const Params &p, const Ba
 }
 
 // ----------------------------------------------------------------------------
+// stage 1, team path (k_fragments_team): the same bytes as build_fragments_fast<false, kS1Units> - every unit
+// of the six strings of a mate, the fragment list, ReadMeta, the error flags - with a team of 16 lanes per read.  The
+// one-lane-per-read kernel stores 16 bytes per lane to 64 different cache lines per instruction and loads the nucleotides the
+// same way; a team moves whole runs of contiguous bytes:
+//   * lane j loads bytes [12j, 12j + 16) of the mate (five aligned dwords, neighbouring lanes 12 bytes apart) and translates
+//     codons 4j .. 4j+3 of the three frames of both strands: one dword per string, forward ones at dword j of their string,
+//     reverse ones (byte-swapped) at dword 4u - 1 - j;
+//   * the dwords meet in the team's LDS and leave as whole 16-byte units, at most two stores per lane and mate;
+//   * the no-stop masks: a nibble per lane and string, two lanes' nibbles per byte (Team::xor1), a 64-bit word per string;
+//   * lane f < 6 takes the runs of string f (s1_runs' arithmetic) and appends them to the team's LDS list; the list order is
+//     then found by counting, lane k ranking entries k and k + 16.  The order of the appends does not matter: no two
+//     fragments of a read share an emission moment, so the ranked (or, beyond kS1ListCap, sorted) list is the same.
+// The function is written for Team::kSlots lanes per call: on the device the calling lane alone (S1TeamDev), on the host all
+// sixteen, phase by phase (S1TeamHost, tests/emu/stage1_team_emu.cpp).  Team::sync() separates the phases.
+// ----------------------------------------------------------------------------
+constexpr uint32_t kS1TeamLanes = 16;
+struct S1TeamLds {                     // per team (640 bytes, 16-byte aligned)
+  u128 str[6 * kS1Units];              // the six strings of the mate at hand, unit by unit as they go to memory
+  uint64_t ns[6];                      // per string: bit i = the residue of codon i is no stop
+  uint32_t hi[kS1ListCap], lo[kS1ListCap];   // the list as found: build_fragments_fast's two words per fragment
+  uint32_t n, pad[3];                  // fragments appended
+};
+static_assert(sizeof(S1TeamLds) % 16 == 0, "S1TeamLds is an array of 16-byte aligned team areas");
+
+struct S1TeamHost {                    // the sixteen lanes of a team one after the other (host emulation)
+  static constexpr int kSlots = (int)kS1TeamLanes;
+  S1TeamLds *lds;
+  KJ_HD uint32_t lane(int s) const { return (uint32_t)s; }
+  KJ_HD void sync() const {}
+  KJ_HD void sync_memory() const {}
+  KJ_HD uint32_t xor1(const uint32_t *v, int s) const { return v[s ^ 1]; }
+  // dword of the mate at s whose first byte is s[at] (-3 <= at < len): bytes outside the mate read as 0 (masked by the caller)
+  KJ_HD uint32_t dword(const uint8_t *s, uint32_t len, int32_t at) const {
+    uint32_t v = 0;
+    for (int32_t i = 0; i < 4; i++) if (at + i >= 0 && at + i < (int32_t)len) v |= (uint32_t)s[at + i] << (8 * i);
+    return v;
+  }
+};
+#if defined(__HIPCC__)
+struct S1TeamDev {                     // the calling lane: lane j of the team in lanes 16t .. 16t+15 of its wavefront
+  static constexpr int kSlots = 1;
+  S1TeamLds *lds;
+  uint32_t j;
+  KJ_HD uint32_t lane(int) const { return j; }
+  // the team's lanes are in one wavefront: LDS traffic between them needs no barrier, only the compiler kept in order
+  KJ_HD void sync() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+  }
+  KJ_HD void sync_memory() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __threadfence();
+#endif
+  }
+  KJ_HD uint32_t xor1(const uint32_t *v, int) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v[0], 0xB1, 0xF, 0xF, false);     // quad_perm [1, 0, 3, 2]
+#else
+    return v[0];
+#endif
+  }
+  KJ_HD uint32_t dword(const uint8_t *s, uint32_t, int32_t at) const { return *reinterpret_cast<const uint32_t *>(s + at); }
+};
+#endif
+
+// bit k = byte k of w is not 0 (bytes below 128: index-alphabet codes)
+KJ_HD uint32_t s1_nz4(uint32_t w) { return (((w + 0x7f7f7f7fu) & 0x80808080u) * 0x00204081u) >> 28; }
+
+// one mate: its strings to area (16-byte aligned), its fragments to the team's list.  off: where the mate's strings start in
+// the read's area, seq_base: its first emission moment (s1_runs)
+template <class Team>
+KJ_HD void s1_team_mate(const Stage1Tables &t, const Params &p, const Team &tm, const uint8_t *s, uint32_t len, uint8_t *area,
+                        uint32_t off, uint32_t seq_base, Frag *list, uint32_t cap) {
+  constexpr int W = Team::kSlots;
+  S1TeamLds &L = *tm.lds;
+  uint32_t *str32 = reinterpret_cast<uint32_t *>(L.str);
+  uint8_t *ns8 = reinterpret_cast<uint8_t *>(L.ns);
+  const uint32_t u = len / 48u + 1u;
+  uint32_t X[W];
+  for (int sl = 0; sl < W; sl++) {                           // translation: codons 4j .. 4j+3 of all six strings
+    const uint32_t j = tm.lane(sl), from = 12u * j;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};                         // bytes [from, from + 16) of the mate, zeros behind its end
+    if (from < len) {
+      const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(s + from) & 3u);
+      uint32_t d[5];
+#pragma unroll
+      for (int k = 0; k < 5; k++) {
+        const int32_t at = (int32_t)(from + 4u * (uint32_t)k) - (int32_t)a;
+        d[k] = at < (int32_t)len ? tm.dword(s, len, at) : 0u;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) w[k] = (uint32_t)((((uint64_t)d[k + 1] << 32) | d[k]) >> (8u * a));
+      const uint32_t v = len - from;
+      if (v < 16u) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t q = 4u * (uint32_t)k;
+          w[k] &= q >= v ? 0u : (q + 4u <= v ? 0xffffffffu : (1u << (8u * (v - q))) - 1u);
+        }
+      }
+    }
+    uint32_t c[14];
+#pragma unroll
+    for (int q = 0; q < 14; q++) c[q] = t.nuc3[(w[q >> 2] >> (8 * (q & 3))) & 255u];
+    uint32_t x = 0;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+      uint32_t F = 0, R = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t idx = c[3 * k + g] << 6 | c[3 * k + g + 1] << 3 | c[3 * k + g + 2];
+        F |= (uint32_t)t.tf[idx] << (8 * k);
+        R |= (uint32_t)t.tr[idx] << (8 * k);
+      }
+      x |= s1_nz4(F) << (4 * g) | s1_nz4(R) << (4 * (3 + g));
+      if (j < 4u * u) {
+        str32[(uint32_t)g * 4u * u + j] = F;
+        str32[(uint32_t)(3 + g) * 4u * u + 4u * u - 1u - j] = __builtin_bswap32(R);
+      }
+    }
+    X[sl] = j < 4u * u ? x : 0u;
+  }
+  for (int sl = 0; sl < W; sl++) {                           // the masks: lanes 2i and 2i + 1 make byte i of each
+    const uint32_t j = tm.lane(sl), y = tm.xor1(X, sl);
+    if (!(j & 1u)) {
+#pragma unroll
+      for (int f = 0; f < 6; f++) ns8[8 * f + j / 2u] = (uint8_t)(((X[sl] >> (4 * f)) & 15u) | ((y >> (4 * f)) & 15u) << 4);
+    }
+  }
+  tm.sync();
+  const uint32_t m = p.m;
+  for (int sl = 0; sl < W; sl++) {
+    const uint32_t j = tm.lane(sl);
+    for (uint32_t k = j; k < 6u * u; k += kS1TeamLanes) *reinterpret_cast<u128 *>(area + 16u * k) = L.str[k];
+    if (j >= 6u || m > 64u || m == 0u) continue;
+    // the runs of string f = j, as s1_runs
+    const int f = (int)j;
+    const uint32_t g = f < 3 ? (uint32_t)f : (uint32_t)f - 3u;
+    const uint32_t top = len - 3, seqF = seq_base, seqR = seq_base + len + 3;
+    uint64_t E = L.ns[f];
+    uint32_t wd = 1;
+    while (2 * wd <= m) { E &= E >> wd; wd *= 2; }
+    if (wd < m) E &= E >> (m - wd);
+    while (E) {
+      const uint32_t a = mk_ctz(E);
+      uint32_t run = 0;
+      E = mk_clear_lowest_run(E, run);
+      const uint32_t l = run + m - 1;
+      uint32_t seq;
+      if (f < 3) {
+        const uint32_t ps = 3 * (a + l) + g;
+        seq = ps <= top ? seqF + ps : seqF + len + g;
+      } else {
+        seq = a == 0 ? seqR + len + g : seqR + (top - (3 * (a - 1) + g));
+      }
+      const uint32_t st = s1_start(f, u, a, l);
+      uint32_t key = l;
+      if (p.mode == 1) {
+        const uint8_t *pep = reinterpret_cast<const uint8_t *>(L.str) + st;
+        key = 0;
+        for (uint32_t x = 0; x < l; x++) key += t.diag[pep[x]];
+        if (key < p.min_score) continue;
+      }
+      const uint32_t slot = append_slot(&L.n);
+      if (slot >= cap) continue;                              // cannot happen: cap is a proven bound
+      if (slot < (uint32_t)kS1ListCap) {
+        L.hi[slot] = key << 11 | (2047u - seq);
+        L.lo[slot] = (off + st) << 8 | l << 1;
+      } else {
+        Frag fr; fr.start = off + st; fr.len = l; fr.key = key; fr.flags = seq << 1;
+        list[slot] = fr;
+      }
+    }
+  }
+  tm.sync();
+}
+
+template <class Team>
+KJ_HD void build_fragments_team(const Stage1Tables &t, const Params &p, const Batch &b, uint32_t r, uint32_t *err_flags,
+                                const Team &tm) {
+  constexpr int W = Team::kSlots;
+  S1TeamLds &L = *tm.lds;
+  const uint64_t o0 = b.off[2 * (uint64_t)r], o1 = b.off[2 * (uint64_t)r + 1], o2 = b.off[2 * (uint64_t)r + 2];
+  uint32_t len1 = (uint32_t)(o1 - o0), len2 = (uint32_t)(o2 - o1);
+  const uint32_t m3 = p.m * 3;
+  const uint32_t fbase = (uint32_t)frag_base(b.off, r, p.m);
+  Frag *list = b.frags + fbase;
+  const uint32_t cap = frag_cap(b.off, r, p.m);
+  const uint64_t pbase = pep_base(b.off, r);
+  uint32_t n = 0;
+  if (len1 > kS1MaxLen || len2 > kS1MaxLen) {
+    if (err_flags) *err_flags |= kErrReadTooLong;
+    len1 = len2 = 0;
+  }
+  const bool skip = b.paired ? (len1 < m3 && len2 < m3) : (len1 < m3);     // length gate, ConsumerThread.cpp:647-654
+  if (!skip) {
+    for (int sl = 0; sl < W; sl++) if (tm.lane(sl) == 0) L.n = 0;
+    tm.sync();
+    uint8_t *area = b.pep + pbase;
+    const uint32_t mate_bytes = len1 >= m3 ? 96u * (len1 / 48u + 1u) : 0u;
+    if (len1 >= m3) s1_team_mate(t, p, tm, b.seqs + o0, len1, area, 0, 0, list, cap);
+    if (b.paired && len2 >= m3) s1_team_mate(t, p, tm, b.seqs + o1, len2, area + mate_bytes, mate_bytes, 2 * len1 + 6, list, cap);
+    n = L.n < cap ? L.n : cap;
+    if (n <= (uint32_t)kS1ListCap) {
+      for (int sl = 0; sl < W; sl++) {                       // rank by counting
+        for (uint32_t e = tm.lane(sl); e < n; e += kS1TeamLanes) {
+          const uint32_t hi = L.hi[e], lo = L.lo[e];
+          uint32_t rank = 0;
+          for (uint32_t q = 0; q < n; q++) rank += L.hi[q] > hi ? 1u : 0u;
+          Frag f; f.start = lo >> 8; f.len = (lo >> 1) & 127u; f.key = hi >> 11; f.flags = 0;
+          list[rank] = f;
+        }
+      }
+    } else {
+      tm.sync_memory();                                      // (the entries beyond kS1ListCap were stored by other lanes)
+      for (int sl = 0; sl < W; sl++) {
+        if (tm.lane(sl) != 0) continue;
+        for (uint32_t k = 0; k < (uint32_t)kS1ListCap; k++) {
+          Frag f; f.start = L.lo[k] >> 8; f.len = (L.lo[k] >> 1) & 127u; f.key = L.hi[k] >> 11; f.flags = (2047u - (L.hi[k] & 2047u)) << 1;
+          list[k] = f;
+        }
+        for (uint32_t k = 1; k < n; k++) {                   // insertion sort in place
+          const Frag f = list[k];
+          uint32_t pos = k;
+          while (pos > 0 && (list[pos - 1].key < f.key || (list[pos - 1].key == f.key && list[pos - 1].flags > f.flags))) {
+            list[pos] = list[pos - 1]; pos--;
+          }
+          list[pos] = f;
+        }
+        for (uint32_t k = 0; k < n; k++) list[k].flags = 0;
+      }
+    }
+  }
+  for (int sl = 0; sl < W; sl++) {
+    if (tm.lane(sl) != 0) continue;
+    ReadMeta rm; rm.pep = pbase; rm.frag = fbase; rm.nfrag = n;
+    b.meta[r] = rm;
+  }
+}
+
+// ----------------------------------------------------------------------------
 // stage 1 for protein input (kaiju -p: ConsumerThread.cpp:640-646,659-696; kaijup: ConsumerThreadp.cpp:17-63):
 // the read is upper-cased and split at every character that is not one of the 20 amino acids; runs of at
 // least m residues (Greedy: scoring at least min_score) become the fragments, in left-to-right order behind
