@@ -39,6 +39,9 @@
 extern "C" {
 #endif
 
+/* The version counts changes that break a caller built against an older header: a struct whose layout changes, a function
+   whose arguments or meaning change, a function that goes away.  New functions (and the structs only they use) leave it
+   as it is. */
 #define KAIJU_GPU_ABI_VERSION 1
 #define KAIJU_GPU_MAX_IDS 21   /* ids_from_SI stops once the set holds > max_match_ids (20) ids */
 
@@ -244,6 +247,33 @@ int kaiju_gpu_get_stats(kaiju_gpu_ctx *ctx, kaiju_gpu_stats *stats);
 #define KAIJU_GPU_N_OP_COUNTS 20
 int kaiju_gpu_set_count_ops(kaiju_gpu_ctx *ctx, int on);
 int kaiju_gpu_get_op_counts(kaiju_gpu_ctx *ctx, uint64_t *out, uint32_t n_out);
+/* Diagnostics: what the device SEG pass (low-complexity masking, the reference's SeqBufferSeg blast_seg.c:2278-2332) computed,
+   fragment by fragment.  ctx: created with input_is_protein and seg; seqs / off: a batch of protein reads in the layout of
+   kaiju_gpu_classify_batch (mates empty).  The reads go through the stage 1 of protein reads (fragments between the
+   separators, those with a 12-window at the SEG trigger entropy queued) and the queue through the SEG launch of the
+   classification path - exact = 0: the SEG pass proper (one wavefront per fragment, or teams of KAIJU_GPU_SEG_TEAM lanes),
+   records of 15 regions with 16-bit positions; exact = 1: the SEG kernel of the exact pass with its scratch, region lists of
+   any length.  As in kaiju_gpu_classify_batch the longest read of the batch, taken from off[], sizes that scratch (what
+   kaiju_gpu_set_max_read_length() says serves the device-resident entry points only).  Nothing is searched; the call blocks.  Per fragment of every read, in the order of the read's fragment list,
+   one kaiju_gpu_seg_fragment; regions are (left, right) pairs of int32, positions relative to the fragment's first residue,
+   at lr[2 * first .. 2 * (first + n_lr)).  At most frag_cap records and lr_cap pairs are written; *n_frags and *n_lr are
+   what the batch has (call again with more room if they exceed the capacities).  kaiju_gpu_get_stats() afterwards reports
+   the queued fragments and the error flags of this call. */
+#define KAIJU_GPU_SEG_LOST 0xffffffffu   /* n of a fragment whose regions found no room in the pool of the exact pass */
+typedef struct {
+  uint32_t read;        /* the read the fragment belongs to                                                           */
+  uint32_t start, len;  /* its first residue in the read, its length                                                   */
+  uint32_t flagged;     /* 1: stage 1 queued it for the SEG pass (0: n, overflow, n_lr are 0)                          */
+  uint32_t n;           /* regions: exact = 0 the record's count (<= 15), exact = 1 all of them or KAIJU_GPU_SEG_LOST  */
+  uint32_t overflow;    /* exact = 0: the record's flag - more than 15 regions, more raw segments than the scan lists  */
+                        /* hold, or more than 65535 residues: the classification path sends such a read to the exact pass */
+  uint32_t n_lr;        /* pairs at lr[2 * first ..): exact = 0 all 15 of the record (unused ones 0), exact = 1 n       */
+  uint32_t reserved;
+  uint64_t first;
+} kaiju_gpu_seg_fragment;
+int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int exact,
+                          kaiju_gpu_seg_fragment *frags, uint64_t frag_cap, uint64_t *n_frags,
+                          int32_t *lr, uint64_t lr_cap, uint64_t *n_lr);
 
 /* ---- host side of the seam ------------------------------------------- */
 int kaiju_taxonomy_load(const char *nodes_dmp_path, kaiju_taxonomy **out);

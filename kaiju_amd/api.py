@@ -55,6 +55,10 @@ HIT_DTYPE = np.dtype([("best", "<u4"), ("n_ids", "<u4"), ("flags", "<u4"), ("res
 RESULT_DTYPE = np.dtype([("taxon", "<u8"), ("best", "<u4"), ("classified", "u1"), ("pad", "u1", (3,))])
 VERBOSE_DTYPE = np.dtype([("n_acc", "<u4"), ("text_len", "<u4"), ("truncated", "<u4"), ("acc_iseq", "<u4", (20,))])  # kaiju_gpu_verbose
 COMPACT_DTYPE = np.dtype([("lca", "<u8"), ("best", "<u4"), ("info", "<u4")])     # kaiju_gpu_compact
+SEG_FRAGMENT_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("len", "<u4"), ("flagged", "<u4"), ("n", "<u4"),
+                               ("overflow", "<u4"), ("n_lr", "<u4"), ("reserved", "<u4"), ("first", "<u8")])   # kaiju_gpu_seg_fragment
+SEG_LOST = 0xffffffff
+assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
 
@@ -112,6 +116,8 @@ def lib():
                                                    C.c_void_p]
     L.kaiju_gpu_set_count_ops.argtypes = [C.c_void_p, C.c_int]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -428,6 +434,24 @@ class Classifier:
         v = np.zeros(len(self.OP_COUNT_NAMES), dtype=np.uint64)
         _check(lib().kaiju_gpu_get_op_counts(self._h, v.ctypes.data, len(v)))
         return {k: int(x) for k, x in zip(self.OP_COUNT_NAMES, v)}
+
+    def seg_regions(self, seqs: np.ndarray, off: np.ndarray, exact=False):
+        """diagnostics (kaiju_gpu_seg_regions; protein contexts with seg): what the device SEG pass computed for every
+        fragment of the batch - (kaiju_gpu_seg_fragment records, the (left, right) pairs they point into); exact: the SEG
+        kernel of the exact pass instead of the SEG pass proper"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = (len(off) - 1) // 2
+        fcap, lcap = 2 * n + 64, 16 * n + 1024
+        while True:
+            frags = np.zeros(fcap, dtype=SEG_FRAGMENT_DTYPE)
+            lr = np.zeros((lcap, 2), dtype=np.int32)
+            nf, nl = C.c_uint64(0), C.c_uint64(0)
+            _check(lib().kaiju_gpu_seg_regions(self._h, seqs.ctypes.data, off.ctypes.data, n, 1 if exact else 0,
+                                               frags.ctypes.data, fcap, C.byref(nf), lr.ctypes.data, lcap, C.byref(nl)))
+            if nf.value <= fcap and nl.value <= lcap:
+                return frags[: nf.value], lr[: nl.value]
+            fcap, lcap = max(fcap, nf.value), max(lcap, nl.value)
 
     def lca(self, dtax: "DeviceTaxonomy", hits: np.ndarray) -> np.ndarray:
         """host hit records -> compact records through the LCA kernel (blocking)"""

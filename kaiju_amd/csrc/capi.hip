@@ -2077,6 +2077,15 @@ static void launch_seg(const kaiju_gpu_ctx *c, hipStream_t s, const Params &p, c
     default: hipLaunchKernelGGL(k_seg, grid, blk, 0, s, p, st, b, sq); break;
   }
 }
+// the exact pass: reads its list holds, fragments of its queue, (left, right) pairs of its pool; SEG scratch of k_redo_seg
+// for fragments of up to max_frag residues (per block 4 * cap_ints ints and cls_bytes bytes)
+constexpr uint32_t kRedoReads = 1u << 16, kRedoFrags = 1u << 18, kRedoPairs = 1u << 22;
+static void size_redo_seg(ExactPassLaunch &xp, uint64_t max_frag) {
+  xp.cap_ints = (uint32_t)(2 * max_frag + 4);
+  xp.cls_bytes = (uint32_t)((max_frag + 64) & ~63ull);
+  const uint64_t per_block = 16ull * xp.cap_ints + xp.cls_bytes;
+  xp.seg_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (256ull << 20) / per_block));
+}
 // KAIJU_GPU_CALL_TIMES=1: host-side marks of a classification call on stderr (ms since the first mark; which thread) - where a
 // call's wall time goes when it is not in the kernels (allocations of a context's first call, copies, waits)
 static void call_mark(const char *what) {
@@ -2198,15 +2207,11 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
   // the exact pass (kj_core.h: BigSeg; kernels in exact_pass.hip): reads with a fragment whose SEG regions did not fit
   // a SegRec are classified again behind the retry pass, with region lists of any length.  Counters: [5] listed reads,
   // [6] fragments of its queue, [7] its work counter, [20] pairs handed out of its pool
-  constexpr uint32_t kRedoReads = 1u << 16, kRedoFrags = 1u << 18, kRedoPairs = 1u << 22;
   const bool exact_pass = n > 0 && p.seg && c->exact_pass;
   ExactPassLaunch xp{};
   if (exact_pass) {
     const uint64_t max_frag = protein ? max_read_len / 3 : max_read_len / 3 + 2;     // (max_read_len was tripled for protein reads)
-    xp.cap_ints = (uint32_t)(2 * max_frag + 4);
-    xp.cls_bytes = (uint32_t)((max_frag + 64) & ~63ull);
-    const uint64_t per_block = 16ull * xp.cap_ints + xp.cls_bytes;
-    xp.seg_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (256ull << 20) / per_block));
+    size_redo_seg(xp, max_frag);
     if ((rc = ensure(c->redo_bitmap, ((size_t)n / 32 + 2) * 4))) return rc;
     if ((rc = ensure(c->redo_list, (size_t)kRedoReads * 4))) return rc;
     if ((rc = ensure(c->redo_items, (size_t)kRedoFrags * sizeof(SegWork)))) return rc;
@@ -2788,6 +2793,146 @@ extern "C" int kaiju_gpu_get_op_counts(kaiju_gpu_ctx *ctx, uint64_t *out, uint32
   KJ_HIP(hipMemcpy(v, static_cast<const uint8_t *>(ctx->counters.p) + kOpcOffsetBytes, sizeof v, hipMemcpyDeviceToHost));
   for (uint32_t x = 0; x < n_out && x < (uint32_t)kOpcN; x++) out[x] = v[x];
   return KAIJU_GPU_OK;
+}
+
+// Diagnostics: what the device SEG pass computed for every fragment of a batch of protein reads (include/kaiju_gpu.h).
+// Stage 1 (k_fragments_protein) and the SEG launch of launch_batch - launch_seg, or k_redo_seg with the exact pass's scratch -
+// on the buffers launch_batch uses; no search.  Blocking.
+extern "C" int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int exact,
+                                     kaiju_gpu_seg_fragment *frags, uint64_t frag_cap, uint64_t *n_frags,
+                                     int32_t *lr, uint64_t lr_cap, uint64_t *n_lr) {
+  return guarded([&]() -> int {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  if (!ctx || !off || !n_frags || !n_lr || (!frags && frag_cap) || (!lr && lr_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  *n_frags = *n_lr = 0;
+  kaiju_gpu_ctx *c = ctx;
+  const kaiju_gpu_index *ix = c->ix;
+  const Params &p = c->kp;
+  if (!(p.flags & kParamProtein) || !p.seg) return fail(KAIJU_GPU_ERR_ARG, "kaiju_gpu_seg_regions needs a context with input_is_protein and seg");
+  if (n_reads == 0) return KAIJU_GPU_OK;
+  KJ_HIP(hipSetDevice(ix->device));
+  if (off[0] != 0) return fail(KAIJU_GPU_ERR_ARG, "off[0] must be 0");
+  const uint32_t n = n_reads;
+  const uint64_t seq_bytes = off[2 * (uint64_t)n];
+  uint64_t max_len = 1;
+  for (uint64_t r = 0; r < n; r++) {
+    if (off[2 * r + 1] < off[2 * r] || off[2 * r + 2] != off[2 * r + 1]) return fail(KAIJU_GPU_ERR_ARG, "offsets must be non-decreasing, mates empty");
+    const uint64_t l = off[2 * r + 1] - off[2 * r];
+    if (l > 0x10000000ull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "protein read longer than 2^28");
+    if (l > max_len) max_len = l;
+  }
+  if (seq_bytes && !seqs) return fail(KAIJU_GPU_ERR_ARG, "seqs is NULL");
+  // the buffers of launch_batch, sized as there
+  const uint64_t pep_bytes = 2 * seq_bytes + kPepPerRead * n + 32 + 256;
+  const uint64_t n_frag_slots = 2 * ((2 * seq_bytes) / (p.m + 1) + 7ull * n) + 8;
+  if (n_frag_slots >= 0xffffffffull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "batch too large: split it (fragment slots exceed 2^32)");
+  const uint64_t seg_cap = std::min<uint64_t>(n_frag_slots / 2 + 8, 0x00ffffffull);
+  int rc;
+  if ((rc = ensure(c->h_seqs, seq_bytes + 64))) return rc;
+  if ((rc = ensure(c->h_off, (2 * (size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(c->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
+  if ((rc = ensure(c->pep, pep_bytes))) return rc;
+  if ((rc = ensure(c->frags, n_frag_slots * sizeof(Frag)))) return rc;
+  if ((rc = ensure(c->meta, (size_t)n * sizeof(ReadMeta) + 16))) return rc;
+  if ((rc = ensure(c->counters, 4096))) return rc;
+  if ((rc = ensure(c->seg_items, seg_cap * sizeof(SegWork)))) return rc;
+  if ((rc = ensure(c->seg_recs, seg_cap * sizeof(SegRec)))) return rc;
+  ExactPassLaunch xp{};
+  if (exact) {
+    size_redo_seg(xp, max_len);
+    if ((rc = ensure(c->redo_index, (size_t)std::max<uint64_t>(seg_cap, kRedoFrags) * sizeof(uint2)))) return rc;
+    if ((rc = ensure(c->redo_pool, (size_t)kRedoPairs * 8))) return rc;
+    if ((rc = ensure(c->redo_work, (size_t)xp.seg_blocks * 16 * xp.cap_ints))) return rc;
+    if ((rc = ensure(c->redo_cls, (size_t)xp.seg_blocks * xp.cls_bytes))) return rc;
+  }
+  hipStream_t s = c->stream;
+  if (seq_bytes) KJ_HIP(hipMemcpyAsync(c->h_seqs.p, seqs, seq_bytes, hipMemcpyHostToDevice, s));
+  KJ_HIP(hipMemcpyAsync(c->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+  Batch b;
+  b.seqs = static_cast<const uint8_t *>(c->h_seqs.p); b.off = static_cast<const uint64_t *>(c->h_off.p); b.n_reads = n; b.paired = 0;
+  b.pep = static_cast<uint8_t *>(c->pep.p); b.frags = static_cast<Frag *>(c->frags.p);
+  b.meta = static_cast<ReadMeta *>(c->meta.p); b.hits = static_cast<Hit *>(c->h_hits.p);
+  uint32_t *cnt = static_cast<uint32_t *>(c->counters.p);
+  SegQueue sq;
+  sq.items = static_cast<SegWork *>(c->seg_items.p); sq.recs = static_cast<SegRec *>(c->seg_recs.p);
+  sq.count = cnt + 4; sq.cap = (uint32_t)seg_cap;
+  KJ_HIP(hipMemsetAsync(cnt, 0, 1024, s));
+  KJ_HIP(hipEventRecord(c->ev[0], s));
+  hipLaunchKernelGGL(k_fragments_protein, dim3((n + kFragBlock - 1) / kFragBlock), dim3(kFragBlock), 0, s, ix->d_ct, p, ix->st, b, sq, cnt + 3);
+  KJ_HIP(hipGetLastError());
+  KJ_HIP(hipEventRecord(c->ev[1], s));
+  if (!exact) {
+    launch_seg(c, s, p, ix->st, b, sq);
+    KJ_HIP(hipGetLastError());
+  } else {
+    xp.st = ix->st; xp.b = b; xp.cnt = cnt; xp.stream = s;
+    xp.sq2 = SegQueue{sq.items, nullptr, sq.count, sq.cap};               // stage 1's queue is the exact pass's here
+    xp.big = BigSeg{static_cast<uint2 *>(c->redo_index.p), static_cast<int32_t *>(c->redo_pool.p), cnt + 20, kRedoPairs};
+    xp.work = static_cast<int32_t *>(c->redo_work.p); xp.cls = static_cast<uint8_t *>(c->redo_cls.p);
+    KJ_HIP(kj_launch_redo_seg(xp));
+  }
+  for (int e = 2; e <= 4; e++) KJ_HIP(hipEventRecord(c->ev[e], s));
+  c->ev_valid = true;
+  c->last_n = n;
+  KJ_HIP(hipStreamSynchronize(s));
+  // the fragment lists, the queue and what the SEG kernels wrote
+  uint32_t hc[24];
+  KJ_HIP(hipMemcpy(hc, cnt, sizeof hc, hipMemcpyDeviceToHost));
+  const uint32_t queued = std::min<uint32_t>(hc[4], sq.cap);
+  const uint64_t used_slots = frag_base(off, n, p.m);                     // (slots of the reads in front of a read behind the last)
+  std::vector<ReadMeta> hm(n);
+  KJ_HIP(hipMemcpy(hm.data(), c->meta.p, (size_t)n * sizeof(ReadMeta), hipMemcpyDeviceToHost));
+  std::vector<Frag> hf((size_t)used_slots);
+  if (used_slots) KJ_HIP(hipMemcpy(hf.data(), c->frags.p, (size_t)used_slots * sizeof(Frag), hipMemcpyDeviceToHost));
+  std::vector<SegRec> hrec;
+  std::vector<uint2> hidx;
+  std::vector<int32_t> hpool;
+  if (!exact) {
+    hrec.resize(queued);
+    if (queued) KJ_HIP(hipMemcpy(hrec.data(), sq.recs, (size_t)queued * sizeof(SegRec), hipMemcpyDeviceToHost));
+  } else {
+    hidx.resize(queued);
+    if (queued) KJ_HIP(hipMemcpy(hidx.data(), xp.big.index, (size_t)queued * sizeof(uint2), hipMemcpyDeviceToHost));
+    hpool.resize(2 * (size_t)std::min<uint32_t>(hc[20], kRedoPairs));
+    if (!hpool.empty()) KJ_HIP(hipMemcpy(hpool.data(), xp.big.lr, hpool.size() * 4, hipMemcpyDeviceToHost));
+  }
+  uint64_t nf = 0, nl = 0;
+  auto put = [&](int32_t l, int32_t r) {
+    if (nl < lr_cap) { lr[2 * nl] = l; lr[2 * nl + 1] = r; }
+    nl++;
+  };
+  for (uint32_t r = 0; r < n; r++) {
+    const uint32_t cntf = hm[r].nfrag & ~kNfragSegPending;
+    for (uint32_t k = 0; k < cntf; k++) {
+      if ((uint64_t)hm[r].frag + k >= used_slots) return fail(KAIJU_GPU_ERR_HIP, "fragment list outside the slots of the batch");
+      const Frag &f = hf[(size_t)hm[r].frag + k];
+      kaiju_gpu_seg_fragment o{};
+      o.read = r; o.start = f.start; o.len = f.len; o.first = nl;
+      const uint32_t slot1 = f.flags >> kFragSlotShift;                   // queue slot + 1 (build_fragments_protein)
+      if (slot1 && slot1 <= queued) {
+        o.flagged = 1;
+        if (!exact) {
+          const SegRec &rec = hrec[slot1 - 1];
+          o.n = rec.n; o.overflow = rec.overflow; o.n_lr = kSegRecRegions;
+          for (int q = 0; q < kSegRecRegions; q++) put(rec.lr[q][0], rec.lr[q][1]);
+        } else {
+          const uint2 ent = hidx[slot1 - 1];
+          o.n = ent.y;
+          if (ent.y != kBigSegLost) {
+            if ((uint64_t)ent.x + ent.y > hpool.size() / 2) return fail(KAIJU_GPU_ERR_HIP, "region list outside the pool");
+            o.n_lr = ent.y;
+            for (uint32_t q = 0; q < ent.y; q++) put(hpool[2 * ((size_t)ent.x + q)], hpool[2 * ((size_t)ent.x + q) + 1]);
+          }
+        }
+      }
+      if (nf < frag_cap) frags[nf] = o;
+      nf++;
+    }
+  }
+  *n_frags = nf; *n_lr = nl;
+  return KAIJU_GPU_OK;
+  });
 }
 
 extern "C" int kaiju_gpu_synchronize(kaiju_gpu_ctx *ctx) {

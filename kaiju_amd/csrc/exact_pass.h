@@ -35,3 +35,6 @@ struct ExactPassLaunch {
 
 // collect the reads -> stage 1 -> SEG with lists of any length -> (MEM) split -> search; asynchronous on a.stream
 hipError_t kj_launch_exact_pass(const ExactPassLaunch &a);
+// step (3) of it alone - k_redo_seg over the queue a.sq2 into a.big (uses st, b, sq2, big, work, cls, seg_blocks, cap_ints,
+// cls_bytes, cnt, stream): the diagnostic entry point kaiju_gpu_seg_regions
+hipError_t kj_launch_redo_seg(const ExactPassLaunch &a);

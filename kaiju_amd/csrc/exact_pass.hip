@@ -141,6 +141,13 @@ k_redo_greedy(DevIndex ix, const ConstTables *__restrict__ g_ct, Params p, SegQu
   greedy_lane(ix, s_ct, p, sq2, b, wl, gs, vb, &big);
 }
 
+// step (3) alone: SEG with lists of any length over the queue a.sq2
+hipError_t kj_launch_redo_seg(const ExactPassLaunch &a) {
+  hipLaunchKernelGGL(k_redo_seg, dim3(a.seg_blocks), dim3(kXSegBlock), 0, a.stream, a.st, a.b, a.sq2, a.big, a.work, a.cls, a.cap_ints,
+                     a.cls_bytes, a.cnt + 3);
+  return hipGetLastError();
+}
+
 hipError_t kj_launch_exact_pass(const ExactPassLaunch &a) {
   hipStream_t s = a.stream;
   uint32_t *cnt = a.cnt;
@@ -149,9 +156,7 @@ hipError_t kj_launch_exact_pass(const ExactPassLaunch &a) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_redo_fragments, dim3(64), dim3(kXFragBlock), 0, s, a.d_ct, a.p, a.st, a.b, a.sq2, cnt + 3, a.list, cnt + 5);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_redo_seg, dim3(a.seg_blocks), dim3(kXSegBlock), 0, s, a.st, a.b, a.sq2, a.big, a.work, a.cls, a.cap_ints,
-                     a.cls_bytes, cnt + 3);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = kj_launch_redo_seg(a)) != hipSuccess) return e;
   WorkList wl;
   wl.counter = cnt + 7; wl.reads = a.list; wl.n_items_ptr = cnt + 5; wl.n_items = 0;
   wl.retry_list = nullptr; wl.retry_count = nullptr;

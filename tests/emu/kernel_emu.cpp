@@ -6,9 +6,11 @@
 // machine without a GPU.  This library is built and loaded by tests only; the product
 // library (libkaiju_gpu.so) contains no CPU path and fails loudly without a HIP device.
 #include <sys/stat.h>
+#include <ucontext.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -108,6 +110,133 @@ int emu_seg(void *h, const char *aa, int len, int32_t *left, int32_t *right) {
   const bool use_cls = !getenv("KAIJU_EMU_SEG_NOCLS");
   int n = seg_regions(cx, emu_coop(), codes.data(), len, left, right, ov, work, use_cls ? cls.data() : nullptr, [] {});
   return ov ? -1 : n;
+}
+// the same with the `overflow` flag seg_compute would put into the fragment's SegRec (15 regions, 16-bit positions):
+// returns the number of merged regions (up to kSegMaxRegions of them in left / right) whatever the flag says
+int emu_seg_rec(void *h, const char *aa, int len, int32_t *left, int32_t *right, int *overflow) {
+  EmuIndex *ix = (EmuIndex *)h;
+  std::vector<uint8_t> codes((size_t)len + 1);
+  for (int i = 0; i < len; i++) codes[(size_t)i] = ix->packed.trans[(unsigned char)aa[i] & 127];
+  bool ov = false;
+  const SegCtx cx = seg_ctx(ix->st, ix->st.ent_g, ix->st.lnfact);
+  int32_t work[2 * kSegMaxRegions];
+  std::vector<uint8_t> cls((size_t)len + 1);
+  const bool use_cls = !getenv("KAIJU_EMU_SEG_NOCLS");
+  const int n = seg_regions(cx, emu_coop(), codes.data(), len, left, right, ov, work, use_cls ? cls.data() : nullptr, [] {});
+  *overflow = (ov || n > kSegRecRegions || len > 65535) ? 1 : 0;
+  return n;
+}
+
+// ---- the SEG code with W real lanes ---------------------------------------------------------------------------------------
+// Every lane is a context of its own (ucontext: own stack, own registers) that runs seg_regions until it arrives at a barrier
+// and then hands over; a phase ends when every lane stands at a barrier.  The lanes of a phase run one after the other, in
+// ascending order in one phase and descending in the next, so a lane that reads what another lane writes in the SAME phase
+// (a missing barrier) sees the stale value in one of the two orders - deterministically, where threads would need luck.
+// What the lanes share on the device they share here (the prefix counts of s_Trim, the window classes, the values of the
+// reduction); what every lane of a team writes with the same values there (the scan lists and the merged regions in LDS) is
+// private to each lane here and compared afterwards: "every lane computes the same values" (seg_regions) is checked.
+struct LaneSet {
+  static constexpr size_t kStack = 256 << 10;
+  int width = 0;
+  ucontext_t main_ctx;
+  std::vector<ucontext_t> ctx;
+  std::vector<std::vector<uint8_t>> stack;
+  std::vector<char> done;
+  std::function<void(int)> body;
+  uint64_t pref[2 * (kSegPacked + 1)];
+  double rprob[2][64];        // (two sets, used in turn: a reduction needs one barrier, not a second one behind its reads)
+  int rt[2][64];
+  static void entry(unsigned lo, unsigned hi, int lane) {
+    LaneSet *ls = reinterpret_cast<LaneSet *>((uintptr_t)lo | (uintptr_t)hi << 32);
+    ls->body(lane);
+    ls->done[(size_t)lane] = 1;
+    swapcontext(&ls->ctx[(size_t)lane], &ls->main_ctx);
+  }
+  void barrier(int lane) { swapcontext(&ctx[(size_t)lane], &main_ctx); }
+  // false: some lanes were through while others stood at a barrier (they did not take the same path)
+  bool run(int w, std::function<void(int)> f) {
+    width = w; body = std::move(f);
+    ctx.resize((size_t)w); stack.resize((size_t)w); done.assign((size_t)w, 0);
+    for (int l = 0; l < w; l++) {
+      stack[(size_t)l].resize(kStack);
+      getcontext(&ctx[(size_t)l]);
+      ctx[(size_t)l].uc_stack.ss_sp = stack[(size_t)l].data();
+      ctx[(size_t)l].uc_stack.ss_size = kStack;
+      ctx[(size_t)l].uc_link = &main_ctx;
+      const uintptr_t self = reinterpret_cast<uintptr_t>(this);
+      makecontext(&ctx[(size_t)l], (void (*)())entry, 3, (unsigned)(self & 0xffffffffu), (unsigned)(self >> 32), l);
+    }
+    for (bool up = true;; up = !up) {
+      for (int k = 0; k < w; k++) {
+        const int l = up ? k : w - 1 - k;
+        swapcontext(&main_ctx, &ctx[(size_t)l]);
+      }
+      int through = 0;
+      for (int l = 0; l < w; l++) through += done[(size_t)l];
+      if (through == w) return true;
+      if (through) return false;              // (the contexts that wait are dropped with their stacks)
+    }
+  }
+};
+struct CoopLanes {
+  LaneSet *ls;
+  int id, w;
+  bool use_pref;
+  mutable int turn = 0;
+  int lane() const { return id; }
+  int width() const { return w; }
+  uint64_t *pref() const { return use_pref ? ls->pref : nullptr; }
+  void sync() const { ls->barrier(id); }
+  // the butterfly of CoopWave / CoopTeam::reduce_min (capi.hip): in step o lane l looks at lane l ^ o and takes its pair
+  // if that is smaller, or equal with the earlier t.  Every lane publishes its pair, then replays all W lanes of the butterfly
+  void reduce_min(double &prob, int &t) const {
+    const int z = turn;
+    turn ^= 1;
+    ls->rprob[z][id] = prob; ls->rt[z][id] = t;
+    ls->barrier(id);
+    double p[64], np[64];
+    int q[64], nq[64];
+    for (int l = 0; l < w; l++) { p[l] = ls->rprob[z][l]; q[l] = ls->rt[z][l]; }
+    for (int o = w / 2; o > 0; o >>= 1) {
+      for (int l = 0; l < w; l++) {
+        const double op = p[l ^ o];
+        const int ot = q[l ^ o];
+        np[l] = p[l]; nq[l] = q[l];
+        if (op < p[l] || (op == p[l] && ot < q[l])) { np[l] = op; nq[l] = ot; }
+      }
+      for (int l = 0; l < w; l++) { p[l] = np[l]; q[l] = nq[l]; }
+    }
+    prob = p[id]; t = q[id];
+  }
+};
+// SEG of an ASCII peptide by `width` lanes (8, 16, 32 or 64): the number of merged regions, -1 = the scan lists overflowed,
+// -2 = the lanes disagree about the result, -3 = they did not arrive at the same barriers
+int emu_seg_lanes(void *h, const char *aa, int len, int width, int32_t *left, int32_t *right) {
+  EmuIndex *ix = (EmuIndex *)h;
+  if (width != 8 && width != 16 && width != 32 && width != 64) return -4;
+  std::vector<uint8_t> codes((size_t)len + 1);
+  for (int i = 0; i < len; i++) codes[(size_t)i] = ix->packed.trans[(unsigned char)aa[i] & 127];
+  const SegCtx cx = seg_ctx(ix->st, ix->st.ent_g, ix->st.lnfact);
+  std::vector<uint8_t> cls((size_t)len + 1);
+  const bool use_cls = !getenv("KAIJU_EMU_SEG_NOCLS");
+  const bool use_pref = !getenv("KAIJU_EMU_NO_SEG_PREFIX");
+  struct LaneOut { int n = 0; bool ov = false; int32_t work[2 * kSegMaxRegions], left[kSegMaxRegions], right[kSegMaxRegions]; };
+  std::vector<LaneOut> out((size_t)width);
+  static thread_local LaneSet lanes;           // (its stacks are kept between calls)
+  const bool together = lanes.run(width, [&](int l) {
+    LaneOut &o = out[(size_t)l];
+    const CoopLanes coop{&lanes, l, width, use_pref, 0};
+    o.n = seg_regions(cx, coop, codes.data(), len, o.left, o.right, o.ov, o.work, use_cls ? cls.data() : nullptr,
+                      [&] { lanes.barrier(l); });
+  });
+  if (!together) return -3;
+  for (int l = 1; l < width; l++) {
+    const LaneOut &o = out[(size_t)l];
+    if (o.n != out[0].n || o.ov != out[0].ov) return -2;
+    for (int k = 0; k < o.n; k++) if (o.left[k] != out[0].left[k] || o.right[k] != out[0].right[k]) return -2;
+  }
+  for (int k = 0; k < out[0].n; k++) { left[k] = out[0].left[k]; right[k] = out[0].right[k]; }
+  return out[0].ov ? -1 : out[0].n;
 }
 
 // verbose output (columns 6/7) of the next emu_classify calls: first-generation lanes write here

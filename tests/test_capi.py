@@ -56,6 +56,15 @@ def test_no_device_fails_loudly(golden):
     assert "no usable HIP device" in str(e.value)
 
 
+def test_seg_regions_entry_needs_a_device():
+    """kaiju_gpu_seg_regions (diagnostics of the device SEG pass) computes on the device only: without one it says so,
+    with one a call without a context is a bad argument"""
+    L = api.lib()
+    nf, nl = C.c_uint64(7), C.c_uint64(7)
+    rc = L.kaiju_gpu_seg_regions(None, None, None, 0, 0, None, 0, C.byref(nf), None, 0, C.byref(nl))
+    assert rc == (-4 if api.device_count() == 0 else -1)                      # KAIJU_GPU_ERR_NO_DEVICE / KAIJU_GPU_ERR_ARG
+
+
 def test_bad_arguments():
     L = api.lib()
     assert L.kaiju_gpu_index_load(None, 0, None) < 0

@@ -58,6 +58,10 @@ class Emu:
         E.emu_symbol.argtypes = [C.c_void_p, C.c_uint64]
         E.emu_seg.restype = C.c_int
         E.emu_seg.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        E.emu_seg_rec.restype = C.c_int
+        E.emu_seg_rec.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]
+        E.emu_seg_lanes.restype = C.c_int
+        E.emu_seg_lanes.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         E.emu_classify.restype = C.c_int
         E.emu_classify.argtypes = [C.c_void_p, C.POINTER(GP), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                    C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -76,6 +80,23 @@ class Emu:
         n = self.lib.emu_seg(h, aa, len(aa), l, r)
         assert n >= 0
         return [(l[i], r[i]) for i in range(n)]
+
+    def seg_rec(self, h, aa: bytes):
+        """(merged regions - up to the 32 the SEG pass keeps -, the overflow flag its record would carry)"""
+        l = (C.c_int32 * 64)()
+        r = (C.c_int32 * 64)()
+        ov = C.c_int(0)
+        n = self.lib.emu_seg_rec(h, aa, len(aa), l, r, C.byref(ov))
+        return [(l[i], r[i]) for i in range(n)], ov.value
+
+    def seg_lanes(self, h, aa: bytes, width: int):
+        """SEG by `width` lanes, one thread each (emu_seg_lanes): the regions; None = the scan lists overflowed.  Lanes that
+        disagree about the result (-2) or do not meet at the barriers (-3) fail here"""
+        l = (C.c_int32 * 64)()
+        r = (C.c_int32 * 64)()
+        n = self.lib.emu_seg_lanes(h, aa, len(aa), width, l, r)
+        assert n >= -1, (n, width, aa)
+        return None if n < 0 else [(l[i], r[i]) for i in range(n)]
 
     def classify(self, h, params, seqs, off, paired=False, caps=(16, 192, 64), want_frags=False, allow_capacity=False):
         """allow_capacity: return (None, 0) instead of failing when a capacity bound of the kernels was hit
