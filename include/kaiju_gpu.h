@@ -180,9 +180,39 @@ int kaiju_gpu_index_get_info(const kaiju_gpu_index *ix, kaiju_gpu_index_info *in
    and packed on the device (KAIJU_GPU_FMI_STREAM) - can be compared array by array at any size.  out[]: [0] rank blocks,
    [1] count bases, [2] sampled sequence numbers, [3] taxon ids of the samples, [4] terminator rows, [5] taxon id and [6]
    validity per sequence, [7] k-mer table, [8] k-mer lines, [9] text, [10] full suffix array / 40-bit text positions,
-   [11] sequence of every row, [12] k (letters of the k-mer table), [13] C[] ; 0 for an array the index does not have. */
+   [11] dense taxon index of every row (row_tax), [12] k (letters of the k-mer table), [13] C[] ; 0 for an array the index
+   does not have. */
 #define KAIJU_GPU_N_DIGESTS 14
 int kaiju_gpu_index_digest(const kaiju_gpu_index *ix, uint64_t *out, uint32_t n_out);
+/* Diagnostics: the arrays themselves.  kaiju_gpu_index_get_layout() says how many bytes of each array the index holds in
+   HBM (0: it does not have that array) - the digest's twelve in the digest's order, then [12] the taxon id of every dense
+   index (tax_of_dense) - and the scalars a reader of those arrays needs; kaiju_gpu_index_read_array() copies bytes
+   [offset_bytes, offset_bytes + n_bytes) of array `which` to host memory (a bounds-checked device-to-host copy: no kernel
+   runs, nothing is computed).  Digest and reader take pointer and size of an array from one table.  The layouts are those of
+   the loader's HBM arrays (kaiju_amd/csrc/kj_core.h: DevIndex); tests compare them element by element with answers derived
+   from the index file and its FASTA alone (tests/index_truth.py).  Both calls need a HIP device. */
+#define KAIJU_GPU_N_INDEX_ARRAYS 13
+enum {
+  KAIJU_GPU_ARR_RANK_BLOCKS = 0, KAIJU_GPU_ARR_COUNT_BASES = 1, KAIJU_GPU_ARR_SA_SEQ = 2, KAIJU_GPU_ARR_SA_TAXID = 3,
+  KAIJU_GPU_ARR_TERM_ROWS = 4, KAIJU_GPU_ARR_SEQ_TAXID = 5, KAIJU_GPU_ARR_SEQ_VALID = 6, KAIJU_GPU_ARR_KMER_TABLE = 7,
+  KAIJU_GPU_ARR_KMER_LINES = 8, KAIJU_GPU_ARR_TEXT = 9, KAIJU_GPU_ARR_SA_FULL = 10 /* wide: the 40-bit text positions */,
+  KAIJU_GPU_ARR_ROW_TAX = 11, KAIJU_GPU_ARR_TAX_OF_DENSE = 12
+};
+typedef struct kaiju_gpu_index_layout {
+  uint64_t bytes[KAIJU_GPU_N_INDEX_ARRAYS];
+  uint64_t C[22];               /* first row of the suffixes that start with letter c; C[21] = bwtlen                     */
+  uint64_t bwtlen, n_sa, sa_skip;
+  uint32_t nseq, chpt_exp;
+  uint32_t mb_shift;            /* wide: a count base every 2^mb_shift rows                                                */
+  uint32_t kmer_k, kline_k;     /* letters of the words of the k-mer table / of the k-mer lines (0: none)                  */
+  uint32_t tv_shift;            /* wide: a text position for every 2^tv_shift-th row                                       */
+  uint32_t n_dense;             /* entries of tax_of_dense                                                                 */
+  uint32_t beyond_lo, beyond_n, beyond_row;   /* KAIJU_IDX_WARN_SA_SHORT: text positions / a row behind the missing sample */
+  uint32_t wide;                /* 1 = 64-bit positions (count bases, 16-byte k-mer entries)                               */
+  uint32_t reserved;
+} kaiju_gpu_index_layout;
+int kaiju_gpu_index_get_layout(const kaiju_gpu_index *ix, kaiju_gpu_index_layout *out);
+int kaiju_gpu_index_read_array(const kaiju_gpu_index *ix, uint32_t which, uint64_t offset_bytes, uint64_t n_bytes, void *host_out);
 
 /* What the index occupies in HBM, array by array (bytes).  Per index row: rank blocks 2 B; suffix-array sample at exponent e:
    4 / 2^e B of sequence numbers and - indexes below 2^32 rows only - 8 / 2^e B of taxon ids; the k-mer table and its lines

@@ -43,6 +43,17 @@ class IndexFootprint(C.Structure):        # kaiju_gpu_index_footprint
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+INDEX_ARRAYS = ("rank_blocks", "count_bases", "sa_seq", "sa_taxid", "term_rows", "seq_taxid", "seq_valid", "kmer_table",
+                "kmer_lines", "text", "sa_full", "row_tax", "tax_of_dense")      # KAIJU_GPU_ARR_*
+
+
+class IndexLayout(C.Structure):           # kaiju_gpu_index_layout
+    _fields_ = [("bytes", C.c_uint64 * len(INDEX_ARRAYS)), ("C", C.c_uint64 * 22), ("bwtlen", C.c_uint64), ("n_sa", C.c_uint64),
+                ("sa_skip", C.c_uint64)] + [(k, C.c_uint32) for k in
+                                            ("nseq", "chpt_exp", "mb_shift", "kmer_k", "kline_k", "tv_shift", "n_dense",
+                                             "beyond_lo", "beyond_n", "beyond_row", "wide", "reserved")]
+
+
 class Stats(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_seg_fragments", C.c_uint64), ("n_overflow_retries", C.c_uint64),
                 ("error_flags", C.c_uint64),
@@ -173,6 +184,25 @@ class Index:
         out = np.zeros(len(self.DIGEST_NAMES), dtype=np.uint64)
         _check(L.kaiju_gpu_index_digest(self._h, out.ctypes.data, len(out)))
         return {k: int(v) for k, v in zip(self.DIGEST_NAMES, out)}
+
+    def layout(self) -> IndexLayout:
+        """kaiju_gpu_index_get_layout: bytes of every array this index holds in HBM (INDEX_ARRAYS order) and its scalars"""
+        L = lib()
+        L.kaiju_gpu_index_get_layout.argtypes = [C.c_void_p, C.POINTER(IndexLayout)]
+        out = IndexLayout()
+        _check(L.kaiju_gpu_index_get_layout(self._h, C.byref(out)))
+        return out
+
+    def read_array(self, name: str, offset: int = 0, n_bytes: int = None) -> np.ndarray:
+        """kaiju_gpu_index_read_array: a slice (default: all) of one array of the index, as bytes"""
+        L = lib()
+        L.kaiju_gpu_index_read_array.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+        which = INDEX_ARRAYS.index(name)
+        if n_bytes is None:
+            n_bytes = int(self.layout().bytes[which]) - offset
+        out = np.empty(n_bytes, dtype=np.uint8)
+        _check(L.kaiju_gpu_index_read_array(self._h, which, offset, n_bytes, out.ctypes.data))
+        return out
 
     def close(self):
         if self._h:

@@ -1557,7 +1557,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
           } else { d.n_dense = (uint32_t)tax_of_dense.size(); }
         }
         if (ok && (text || row_tax)) {
-          if (text) { (void)hipMemset(text, 0, text_bytes); (void)hipMemset(tpos, 0xff, tpos_bytes); }
+          if (text) { (void)hipMemset(text, 0, text_bytes); (void)hipMemset(tpos, 0xff, tpos_bytes - 16); (void)hipMemset(tpos + tpos_bytes - 16, 0, 16); }   // (all ones: no entry; the pad is zero)
           if (row_tax) (void)hipMemset(row_tax, 0xff, rowtax_bytes);
           (void)hipMemset(d_cnt, 0, 16);
           hipLaunchKernelGGL(k_seq_walk_fill, dim3(blocks), dim3(256), 0, 0, d, d_cnt, t_seq, d_len, d_off, text, tpos, (uint32_t)std::max(tv, 0), row_tax, d_sd);
@@ -1829,23 +1829,8 @@ extern "C" int kaiju_gpu_index_digest(const kaiju_gpu_index *ix, uint64_t *out, 
   if (!ix || !out || n_out < KAIJU_GPU_N_DIGESTS) return fail(KAIJU_GPU_ERR_ARG, "bad argument");
   KJ_HIP(hipSetDevice(ix->device));
   const DevIndex &d = ix->dev;
-  uint64_t nw = 1, nlw = 1;
-  for (uint32_t q = 0; q < d.kmer_k; q++) nw *= 20;
-  for (uint32_t q = 1; q < d.kline_k; q++) nlw *= 20;
-  struct Arr { const void *p; uint64_t bytes; };
-  const Arr arrs[12] = {
-      {d.blocks64, ((d.bwtlen >> 6) + 1) * sizeof(RankBlock64)},
-      {d.mb_base, d.mb_base ? ((d.bwtlen >> d.mb_shift) + 1) * 20 * 8 : 0},
-      {d.sa_iseq, d.n_sa * 4},
-      {d.sa_taxid, d.sa_taxid ? (d.n_sa + 2) * 8 : 0},
-      {d.term_pos, (uint64_t)d.nseq * 8},
-      {d.seq_taxid, (uint64_t)d.nseq * 8},
-      {d.seq_valid, (uint64_t)d.nseq},
-      {d.kmer32 ? (const void *)d.kmer32 : (const void *)d.kmer64, d.kmer_k ? nw * (d.kmer32 ? sizeof(uint2) : sizeof(ulonglong2)) : 0},
-      {d.kline, d.kline ? nlw * kKLineBytes : 0},
-      {d.text, d.text ? ix->fp.text : 0},
-      {d.sa_full ? (const void *)d.sa_full : (const void *)d.sa_tpos5, d.sa_full ? d.bwtlen * 4 : d.sa_tpos5 ? ix->tpos_bytes : 0},
-      {d.row_tax, d.row_tax ? d.bwtlen * 4 : 0}};
+  IndexArr arrs[kIndexArrays];                     // (the digest covers the first twelve: tax_of_dense came later, out[] is ABI)
+  index_arrays(d, ix->fp.text, ix->tpos_bytes, arrs);
   unsigned long long *acc = nullptr;
   KJ_HIP(hipMalloc((void **)&acc, 12 * 8));
   hipError_t e = hipMemset(acc, 0, 12 * 8);
@@ -1865,6 +1850,41 @@ extern "C" int kaiju_gpu_index_digest(const kaiju_gpu_index *ix, uint64_t *out, 
   uint64_t hc = 0;
   for (int a = 0; a < 22; a++) hc = (hc ^ d.C[a]) * 0xD6E8FEB86659FD93ull + 1;
   out[13] = hc;
+  return KAIJU_GPU_OK;
+  });
+}
+
+// Diagnostics: the arrays of an index as they lie in HBM (include/kaiju_gpu.h) - sizes and scalars, and a plain copy of a slice
+static_assert(kIndexArrays == KAIJU_GPU_N_INDEX_ARRAYS, "kj::index_arrays and the header list the same arrays");
+extern "C" int kaiju_gpu_index_get_layout(const kaiju_gpu_index *ix, kaiju_gpu_index_layout *out) {
+  return guarded([&]() -> int {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  if (!ix || !out) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  const DevIndex &d = ix->dev;
+  IndexArr arrs[kIndexArrays];
+  index_arrays(d, ix->fp.text, ix->tpos_bytes, arrs);
+  memset(out, 0, sizeof *out);
+  for (int a = 0; a < kIndexArrays; a++) out->bytes[a] = arrs[a].bytes;
+  for (int a = 0; a < 22; a++) out->C[a] = d.C[a];
+  out->bwtlen = d.bwtlen; out->n_sa = d.n_sa; out->sa_skip = d.sa_skip; out->nseq = d.nseq; out->chpt_exp = d.chpt_exp;
+  out->mb_shift = d.mb_shift; out->kmer_k = d.kmer_k; out->kline_k = d.kline_k; out->tv_shift = d.tv_shift; out->n_dense = d.n_dense;
+  out->beyond_lo = d.beyond_lo; out->beyond_n = d.beyond_n; out->beyond_row = d.beyond_row; out->wide = d.mb_base ? 1u : 0u;
+  return KAIJU_GPU_OK;
+  });
+}
+extern "C" int kaiju_gpu_index_read_array(const kaiju_gpu_index *ix, uint32_t which, uint64_t offset_bytes, uint64_t n_bytes, void *host_out) {
+  return guarded([&]() -> int {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  if (!ix || (!host_out && n_bytes) || which >= (uint32_t)kIndexArrays) return fail(KAIJU_GPU_ERR_ARG, "bad argument");
+  IndexArr arrs[kIndexArrays];
+  index_arrays(ix->dev, ix->fp.text, ix->tpos_bytes, arrs);
+  const IndexArr &a = arrs[which];
+  if (offset_bytes > a.bytes || n_bytes > a.bytes - offset_bytes) return fail(KAIJU_GPU_ERR_ARG, "slice beyond the array");
+  if (n_bytes == 0) return KAIJU_GPU_OK;
+  KJ_HIP(hipSetDevice(ix->device));
+  KJ_HIP(hipMemcpy(host_out, static_cast<const uint8_t *>(a.p) + offset_bytes, n_bytes, hipMemcpyDeviceToHost));
   return KAIJU_GPU_OK;
   });
 }

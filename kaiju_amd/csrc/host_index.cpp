@@ -648,6 +648,7 @@ void PackedIndex::build_text_wide(uint32_t shift) {
   if (off[nseq] + 2 * kTextPad >= kTposNone) return;
   text.assign((size_t)(off[nseq] + 2 * kTextPad), 0);
   sa_tpos5.assign((size_t)(((bwtlen >> shift) + 1) * 5 + 16), 0xff);
+  for (size_t x = sa_tpos5.size() - 16; x < sa_tpos5.size(); x++) sa_tpos5[x] = 0;      // (all ones: no entry; the pad is zero)
   // the row -> dense taxon index table of a wide index (capi.hip builds it where HBM has room; KAIJU_EMU_NO_ROW_TAX: without)
   std::vector<uint32_t> seq_dense;
   const bool rt = !getenv("KAIJU_EMU_NO_ROW_TAX");

@@ -240,6 +240,32 @@ KJ_HD void kline_build_one(const DevIndex &ix, uint32_t k, uint64_t code, uint8_
   for (int x = 0; x < 32; x++) dst[x] = out[x];
 }
 
+// THE table of the arrays an index holds (diagnostics: kaiju_gpu_index_digest, kaiju_gpu_index_get_layout / _read_array and the
+// accessors of the test emulation all take pointer and size from here, so they cannot disagree about what an array is).
+// Order: the digest's.  text_bytes / tpos_bytes: what the loader allocated for text / sa_tpos5 (pads included).
+constexpr int kIndexArrays = 13;
+struct IndexArr { const void *p; uint64_t bytes; };
+inline void index_arrays(const DevIndex &d, uint64_t text_bytes, uint64_t tpos_bytes, IndexArr out[kIndexArrays]) {
+  uint64_t nw = 1, nlw = 1;
+  for (uint32_t q = 0; q < d.kmer_k; q++) nw *= 20;
+  for (uint32_t q = 1; q < d.kline_k; q++) nlw *= 20;
+  const IndexArr a[kIndexArrays] = {
+      {d.blocks64, ((d.bwtlen >> 6) + 1) * sizeof(RankBlock64)},
+      {d.mb_base, d.mb_base ? ((d.bwtlen >> d.mb_shift) + 1) * 20 * 8 : 0},
+      {d.sa_iseq, d.n_sa * 4},
+      {d.sa_taxid, d.sa_taxid ? (d.n_sa + 2) * 8 : 0},
+      {d.term_pos, (uint64_t)d.nseq * 8},
+      {d.seq_taxid, (uint64_t)d.nseq * 8},
+      {d.seq_valid, (uint64_t)d.nseq},
+      {d.kmer32 ? (const void *)d.kmer32 : (const void *)d.kmer64, d.kmer_k ? nw * (d.kmer32 ? sizeof(uint2) : sizeof(ulonglong2)) : 0},
+      {d.kline, d.kline ? nlw * kKLineBytes : 0},
+      {d.text, d.text ? text_bytes : 0},
+      {d.sa_full ? (const void *)d.sa_full : (const void *)d.sa_tpos5, d.sa_full ? d.bwtlen * 4 : d.sa_tpos5 ? tpos_bytes : 0},
+      {d.row_tax, d.row_tax ? d.bwtlen * 4 : 0},
+      {d.tax_of_dense, d.tax_of_dense ? (uint64_t)d.n_dense * 8 : 0}};
+  for (int x = 0; x < kIndexArrays; x++) { out[x] = a[x]; if (!out[x].p || !out[x].bytes) out[x] = IndexArr{nullptr, 0}; }
+}
+
 struct Params {
   int32_t mode;              // 0 MEM, 1 GREEDY
   uint32_t m;                // min_fragment_length

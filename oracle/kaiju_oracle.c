@@ -310,6 +310,21 @@ int64_t ko_update_si(ko_index *f, int ct, const int64_t si[2], int64_t out[2]) {
   return b - a;
 }
 
+void ko_get_suffix(ko_index *f, int64_t i, int32_t *iseq, int64_t *pos);
+/* batched forms for tests/index_truth.py (every row of an index through ctypes is too slow one call at a time): the very
+   functions above, called in a loop.  letters[x] / lf[x] = FMindexCurrent of row k0 + x */
+void ko_fmindex_current_rows(ko_index *f, int64_t k0, int64_t n, uint8_t *letters, int64_t *lf) {
+  for (int64_t x = 0; x < n; x++) {
+    int c = 0;
+    const int64_t v = ko_fmindex_current(f, k0 + x, &c);
+    letters[x] = (uint8_t)c;
+    if (lf) lf[x] = v;
+  }
+}
+void ko_get_suffix_rows(ko_index *f, const int64_t *rows, int64_t n, int32_t *iseq, int64_t *pos) {
+  for (int64_t x = 0; x < n; x++) ko_get_suffix(f, rows[x], &iseq[x], &pos[x]);
+}
+
 /* uchar2long + suffixArray_decode_number, suffixArray.h:37-51 */
 static inline void sa_decode(const ko_index *s, int64_t k, int32_t *iseq, int64_t *pos) {
   g_cnt.sa_decode++;

@@ -71,6 +71,31 @@ uint64_t emu_text_pos(void *h, uint64_t r) {
   const uint8_t *e = pk.sa_tpos5.data() + (size_t)(r >> pk.tv_shift) * 5;
   return (uint64_t)e[0] | (uint64_t)e[1] << 8 | (uint64_t)e[2] << 16 | (uint64_t)e[3] << 24 | (uint64_t)e[4] << 32;
 }
+// every array of the host PackedIndex, as kaiju_gpu_index_get_layout / kaiju_gpu_index_read_array hand out the device's: the
+// same table (kj::index_arrays) over host_view(), the same struct, the same bounds check; 0 or KAIJU_GPU_ERR_ARG
+int emu_index_get_layout(void *h, kaiju_gpu_index_layout *out) {
+  if (!h || !out) return KAIJU_GPU_ERR_ARG;
+  const PackedIndex &pk = ((EmuIndex *)h)->packed;
+  const DevIndex d = pk.host_view();
+  IndexArr arrs[kIndexArrays];
+  index_arrays(d, pk.text.size(), pk.sa_tpos5.size(), arrs);
+  memset(out, 0, sizeof *out);
+  for (int a = 0; a < kIndexArrays; a++) out->bytes[a] = arrs[a].bytes;
+  for (int a = 0; a < 22; a++) out->C[a] = d.C[a];
+  out->bwtlen = d.bwtlen; out->n_sa = d.n_sa; out->sa_skip = d.sa_skip; out->nseq = d.nseq; out->chpt_exp = d.chpt_exp;
+  out->mb_shift = d.mb_shift; out->kmer_k = d.kmer_k; out->kline_k = d.kline_k; out->tv_shift = d.tv_shift; out->n_dense = d.n_dense;
+  out->beyond_lo = d.beyond_lo; out->beyond_n = d.beyond_n; out->beyond_row = d.beyond_row; out->wide = d.mb_base ? 1u : 0u;
+  return 0;
+}
+int emu_index_read_array(void *h, uint32_t which, uint64_t offset_bytes, uint64_t n_bytes, void *host_out) {
+  if (!h || (!host_out && n_bytes) || which >= (uint32_t)kIndexArrays) return KAIJU_GPU_ERR_ARG;
+  const PackedIndex &pk = ((EmuIndex *)h)->packed;
+  IndexArr arrs[kIndexArrays];
+  index_arrays(pk.host_view(), pk.text.size(), pk.sa_tpos5.size(), arrs);
+  if (offset_bytes > arrs[which].bytes || n_bytes > arrs[which].bytes - offset_bytes) return KAIJU_GPU_ERR_ARG;
+  if (n_bytes) memcpy(host_out, static_cast<const uint8_t *>(arrs[which].p) + offset_bytes, (size_t)n_bytes);
+  return 0;
+}
 uint64_t emu_rows_without_sequence(void *h) {
   uint64_t n = 0;
   const PackedIndex &pk = ((EmuIndex *)h)->packed;

@@ -65,6 +65,20 @@ def test_seg_regions_entry_needs_a_device():
     assert rc == (-4 if api.device_count() == 0 else -1)                      # KAIJU_GPU_ERR_NO_DEVICE / KAIJU_GPU_ERR_ARG
 
 
+def test_index_read_back_entries_need_a_device():
+    """kaiju_gpu_index_get_layout / kaiju_gpu_index_read_array (diagnostics: the arrays of an index as they lie in HBM) hand out
+    device memory only: without a device they say so, with one a call without an index is a bad argument"""
+    L = api.lib()
+    lay = api.IndexLayout()
+    want = -4 if api.device_count() == 0 else -1                              # KAIJU_GPU_ERR_NO_DEVICE / KAIJU_GPU_ERR_ARG
+    L.kaiju_gpu_index_get_layout.argtypes = [C.c_void_p, C.POINTER(api.IndexLayout)]
+    L.kaiju_gpu_index_read_array.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    assert L.kaiju_gpu_index_get_layout(None, C.byref(lay)) == want
+    buf = (C.c_uint8 * 16)()
+    assert L.kaiju_gpu_index_read_array(None, 0, 0, 16, buf) == want
+    assert C.sizeof(api.IndexLayout) == 13 * 8 + 22 * 8 + 3 * 8 + 12 * 4
+
+
 def test_bad_arguments():
     L = api.lib()
     assert L.kaiju_gpu_index_load(None, 0, None) < 0

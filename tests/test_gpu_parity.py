@@ -204,6 +204,7 @@ def test_index_image_loads_like_the_fmi(gpu_lib, golden, gidx, tmp_path):
                     os.environ[k] = v
         assert idx2.info.bwtlen == gidx.info.bwtlen and idx2.info.nseq == gidx.info.nseq
         assert idx2.footprint.as_dict() == gidx.footprint.as_dict()
+        assert idx2.digest() == gidx.digest(), env        # (every array in HBM: test_gpu_index_arrays.py checks the host-pack load's)
         for mode in ("mem", "greedy"):
             a = api.Classifier(gidx, api.default_params(mode, seg=1)).classify(golden.seqs, golden.off)
             b = api.Classifier(idx2, api.default_params(mode, seg=1)).classify(golden.seqs, golden.off)
