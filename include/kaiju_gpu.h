@@ -380,6 +380,44 @@ int kaiju_gpu_lca_batch(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const k
 int kaiju_finalize_compact(const kaiju_gpu_params *p, double db_length, const kaiju_gpu_compact *recs,
                            const uint64_t *off, uint32_t n_reads, int paired, kaiju_result *out);
 
+/* ---- record extraction on the device: FASTQ / FASTA text in, seqs / off out ------------------------------ */
+/* What the reference does in its reading loop (kaiju.cpp:288-386) and the command line programs here do on the host
+   (BlockCursor in csrc/host/kaiju_main.cpp), as HIP passes (kaiju_amd/csrc/ingest.hip; the rules: kj_ingest.h).  A text is a
+   block of WHOLE records below 2^32 bytes.  Format and keep_names (kaijup: the name is the whole header line without its
+   first byte) are arguments, nothing is detected.  Out come the buffers of kaiju_gpu_classify_batch_device[_compact]: seqs,
+   the strip()'d letters, and off[2n + 1]; with a second text record r of text 2 is the mate of record r of text 1 and
+   n = min(n_records, n_records2) reads are emitted (the records of the longer text's tail are counted only).  names[r] is
+   where the name of record r lies in text 1. */
+typedef struct kaiju_gpu_name_span { uint32_t pos, len; } kaiju_gpu_name_span;
+typedef struct kaiju_gpu_parse_info {
+  uint32_t n_records, n_records2;  /* records found in text 1 / text 2 (0 when unpaired)                                   */
+  uint32_t max_mate_len;           /* longest stripped mate emitted: what kaiju_gpu_set_max_read_length wants              */
+  uint32_t name_mismatch;          /* first emitted record whose names differ between the texts, ~0u: none                 */
+  uint64_t seq_bytes;              /* bytes written to seqs = off[2 * reads emitted]                                       */
+  uint32_t overflow, reserved;     /* 1: more reads than rec_cap; the first rec_cap are emitted, nothing behind the         */
+                                   /* capacities is written                                                                */
+} kaiju_gpu_parse_info;
+/* All pointers are device pointers on the context's GPU; the text pointers must be 16-byte aligned (KAIJU_GPU_ERR_ARG
+   otherwise).  d_text2 = NULL, bytes2 = 0: unpaired.  Asynchronous on `stream` (NULL: the context's own).  The scratch - a line
+   table sized for the worst case, a text of nothing but '\n': 5 bytes per byte of text - lives in the context and grows
+   when a call needs more. */
+int kaiju_gpu_parse_block_device(kaiju_gpu_ctx *ctx, const void *d_text1, uint64_t bytes1, const void *d_text2, uint64_t bytes2,
+                                 int fastq, int keep_names, uint32_t rec_cap, void *d_seqs /* >= bytes1 + bytes2 */,
+                                 uint64_t *d_off /* 2 * rec_cap + 1 */, kaiju_gpu_name_span *d_names /* rec_cap */,
+                                 kaiju_gpu_parse_info *d_info, void *stream);
+/* The same with host pointers (text up, results down); blocks. */
+int kaiju_gpu_parse_block(kaiju_gpu_ctx *ctx, const char *text1, uint64_t bytes1, const char *text2, uint64_t bytes2, int fastq,
+                          int keep_names, uint32_t rec_cap, char *seqs, uint64_t *off, kaiju_gpu_name_span *names,
+                          kaiju_gpu_parse_info *info);
+/* Text in, 16-byte records out: upload, the passes above, one read-back of *info, kaiju_gpu_set_max_read_length(
+   info->max_mate_len) and kaiju_gpu_classify_batch_device_compact on the same stream; out (n records), off (2n + 1: what
+   kaiju_finalize_compact wants) and names (n) come back.  info->overflow: KAIJU_GPU_ERR_ARG, nothing classified.  A name
+   mismatch or a shorter second text is reported in *info and left to the caller. */
+int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
+                                    const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
+                                    kaiju_gpu_compact *out, uint64_t *off, kaiju_gpu_name_span *names,
+                                    kaiju_gpu_parse_info *info);
+
 /* ---- several processes of a node, one per GPU: the gather --------------- */
 /* BASELINE north star: "reads shard embarrassingly across the GPUs of one node with the index replicated per GPU and per-GPU
    hit lists gathered with a single RCCL gather over xGMI".  The reference has no exchange (its threads append to one output

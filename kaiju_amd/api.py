@@ -69,6 +69,11 @@ COMPACT_DTYPE = np.dtype([("lca", "<u8"), ("best", "<u4"), ("info", "<u4")])    
 SEG_FRAGMENT_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("len", "<u4"), ("flagged", "<u4"), ("n", "<u4"),
                                ("overflow", "<u4"), ("n_lr", "<u4"), ("reserved", "<u4"), ("first", "<u8")])   # kaiju_gpu_seg_fragment
 SEG_LOST = 0xffffffff
+NAME_SPAN_DTYPE = np.dtype([("pos", "<u4"), ("len", "<u4")])                                   # kaiju_gpu_name_span
+PARSE_INFO_DTYPE = np.dtype([("n_records", "<u4"), ("n_records2", "<u4"), ("max_mate_len", "<u4"), ("name_mismatch", "<u4"),
+                             ("seq_bytes", "<u8"), ("overflow", "<u4"), ("reserved", "<u4")])  # kaiju_gpu_parse_info
+NO_MISMATCH = 0xffffffff
+assert NAME_SPAN_DTYPE.itemsize == 8 and PARSE_INFO_DTYPE.itemsize == 32
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -126,6 +131,12 @@ def lib():
     L.kaiju_gpu_classify_batch_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                                    C.c_void_p]
     L.kaiju_gpu_set_count_ops.argtypes = [C.c_void_p, C.c_int]
+    L.kaiju_gpu_parse_block_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kaiju_gpu_parse_block.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kaiju_gpu_classify_text_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -452,6 +463,44 @@ class Classifier:
                                                       1 if paired else 0, out.ctypes.data))
         return out
 
+    def classify_text_compact(self, dtax: "DeviceTaxonomy", text1, text2=None, fastq=True, keep_names=False, rec_cap=None):
+        """FASTQ / FASTA text in, 16-byte records out (kaiju_gpu_classify_text_compact): the records are extracted on the
+        device.  Returns a dict: compact, off, names (n x 2 uint32: position and length in text1), info."""
+        t1, t2, cap = _text_args(text1, text2, rec_cap)
+        out = np.zeros(cap, dtype=COMPACT_DTYPE)
+        off = np.zeros(2 * cap + 1, dtype=np.uint64)
+        names = np.zeros(cap, dtype=NAME_SPAN_DTYPE)
+        info = np.zeros(1, dtype=PARSE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_classify_text_compact(self._h, dtax._h, t1.ctypes.data, len(t1) - 1, t2.ctypes.data if t2 is not None else None,
+                                                     len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
+                                                     out.ctypes.data, off.ctypes.data, names.ctypes.data, info.ctypes.data))
+        n = _reads_emitted(info[0], t2 is not None, cap)
+        return {"compact": out[:n], "off": off[: 2 * n + 1], "names": names[:n].view("<u4").reshape(n, 2), "info": info[0]}
+
+    def parse_block_device(self, d_text1_ptr: int, bytes1: int, d_text2_ptr: int, bytes2: int, rec_cap: int, d_seqs_ptr: int,
+                           d_off_ptr: int, d_names_ptr: int, d_info_ptr: int, fastq=True, keep_names=False, stream: int = 0):
+        """Device-resident text (raw pointers, 16-byte aligned; d_text2_ptr = 0: unpaired) to device-resident seqs / off /
+        names / info (kaiju_gpu_parse_block_device); asynchronous on ``stream``."""
+        _check(lib().kaiju_gpu_parse_block_device(self._h, d_text1_ptr or None, bytes1, d_text2_ptr or None, bytes2, 1 if fastq else 0,
+                                                  1 if keep_names else 0, rec_cap, d_seqs_ptr or None, d_off_ptr or None,
+                                                  d_names_ptr or None, d_info_ptr or None, stream or None))
+
+    def parse_block_tensors(self, text1, text2=None, fastq=True, keep_names=False, rec_cap=None, stream: int = 0):
+        """parse_block_device for torch uint8 tensors on the context's GPU; returns a dict of tensors (seqs uint8, off int64,
+        names int32 n_cap x 2, info: 8 x int32 in the layout of kaiju_gpu_parse_info), nothing is synchronised"""
+        import torch
+        assert text1.dtype == torch.uint8 and text1.is_contiguous() and (text2 is None or (text2.dtype == torch.uint8 and text2.is_contiguous()))
+        b1, b2 = text1.numel(), text2.numel() if text2 is not None else 0
+        cap = int(rec_cap) if rec_cap is not None else b1 + 1
+        dev = text1.device
+        seqs = torch.empty(b1 + b2 + 64, dtype=torch.uint8, device=dev)
+        off = torch.empty(2 * cap + 1, dtype=torch.int64, device=dev)
+        names = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)
+        info = torch.empty(8, dtype=torch.int32, device=dev)
+        self.parse_block_device(text1.data_ptr(), b1, text2.data_ptr() if text2 is not None else 0, b2, cap, seqs.data_ptr(), off.data_ptr(),
+                                names.data_ptr(), info.data_ptr(), fastq=fastq, keep_names=keep_names, stream=stream)
+        return {"seqs": seqs, "off": off, "names": names, "info": info}
+
     OP_COUNT_NAMES = ("kmer_lookups", "update_si", "update_si_lines", "lf_steps", "lf_lines", "sa_samples", "read_meta",
                       "frag_desc", "window_fills", "term_searches", "si_spills", "hits", "multi_letter_steps", "items_read",
                       "matches_read", "items_written", "matches_written", "wave_iterations", "lane_iterations", "record_bytes", "pruned_chains", "window_lines")
@@ -510,3 +559,43 @@ class Classifier:
             self.close()
         except Exception:
             pass
+
+
+Context = Classifier
+
+
+def _text_args(text1, text2, rec_cap):
+    """texts as uint8 arrays with one byte of slack behind them (an empty text still has an address); the capacity: as many
+    records as there are lines unless the caller knows better"""
+    def arr(t):
+        a = np.frombuffer(bytes(t), dtype=np.uint8) if not isinstance(t, np.ndarray) else np.ascontiguousarray(t, dtype=np.uint8)
+        return np.concatenate([a, np.zeros(1, dtype=np.uint8)])
+    t1 = arr(text1)
+    t2 = arr(text2) if text2 is not None else None
+    cap = int(rec_cap) if rec_cap is not None else int(np.count_nonzero(t1[:-1] == 10)) + 1
+    return t1, t2, cap
+
+
+def _reads_emitted(info, paired, cap):
+    n = min(int(info["n_records"]), int(info["n_records2"])) if paired else int(info["n_records"])
+    return min(n, cap)
+
+
+def parse_block(ctx: Classifier, text1, text2=None, fastq=True, keep_names=False, rec_cap=None, names_fill=None):
+    """Record extraction on the device (kaiju_gpu_parse_block): FASTQ / FASTA text (bytes or uint8 arrays; text2: the mates)
+    to the buffers the classification entry points take.  Returns a dict: seqs (uint8), off (uint64, 2n + 1), names
+    (n x 2 uint32: position and length of every name in text1), info (PARSE_INFO_DTYPE record) and names_all, the whole
+    name buffer of rec_cap entries (pre-set to names_fill: what lies behind the reads emitted is not written)."""
+    t1, t2, cap = _text_args(text1, text2, rec_cap)
+    seqs = np.zeros(len(t1) + (len(t2) if t2 is not None else 0), dtype=np.uint8)
+    off = np.zeros(2 * cap + 1, dtype=np.uint64)
+    names = np.zeros(cap + 1, dtype=NAME_SPAN_DTYPE)
+    if names_fill is not None:
+        names.view("<u4")[:] = names_fill
+    info = np.zeros(1, dtype=PARSE_INFO_DTYPE)
+    _check(lib().kaiju_gpu_parse_block(ctx._h, t1.ctypes.data, len(t1) - 1, t2.ctypes.data if t2 is not None else None,
+                                       len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
+                                       seqs.ctypes.data, off.ctypes.data, names.ctypes.data, info.ctypes.data))
+    n = _reads_emitted(info[0], t2 is not None, cap)
+    return {"seqs": seqs[: int(info[0]["seq_bytes"])], "off": off[: 2 * n + 1], "names": names[:n].view("<u4").reshape(n, 2),
+            "info": info[0], "names_all": names[:cap].view("<u4").reshape(cap, 2)}

@@ -40,6 +40,12 @@
 #include "kj_core.h"
 #include "taxonomy.h"
 #include "exact_pass.h"
+#include "kj_ingest.h"
+// Libraries linked from a source list of their own (the compile-time variants of tests/tools/mem_variants.sh: search lanes
+// only) need not hold ingest.hip: the two functions are weak references here, and without them the entry points below say
+// KAIJU_GPU_ERR_UNSUPPORTED.  kaiju_amd/build.py always links ingest.hip.
+__attribute__((weak)) decltype(kj_ingest_launch) kj_ingest_launch;
+__attribute__((weak)) decltype(kj_ingest_free) kj_ingest_free;
 #ifdef KJ_GREEDY3                    // the experimental row-pool Greedy lane: variant builds only
 #include "kj_greedy3.h"
 #endif
@@ -1951,13 +1957,16 @@ struct kaiju_gpu_ctx {
   std::vector<uint8_t> vb_host;      // ... and where it arrives
   std::vector<uint32_t> vb_h_nacc, vb_h_acc;   // (host side of the accessions: kept, so that a call does not fault 80 bytes per read in again)
   DevBuf h_seqs, h_off, h_hits;      // staging for the host-buffer entry point
+  kj_ingest_scratch *ingest = nullptr;                 // record extraction (ingest.hip): line tables, flags, scan partials
+  DevBuf ing_text1, ing_text2, ing_names, ing_info;    // ... and the staging of its host-pointer entry points
   kaiju_gpu_stats stats{};
   uint32_t last_n = 0;
   uint32_t max_read_len = 1024;
   ~kaiju_gpu_ctx() {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
-    DevBuf *all[] = {&pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
+    if (ingest) kj_ingest_free(ingest);
+    DevBuf *all[] = {&ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
                      &vb_nacc, &vb_acc, &vb_tlen, &vb_text, &vb_bestv, &vb_bestv_retry, &vb_packed, &vb_pos,
                      &redo_bitmap, &redo_list, &redo_items, &redo_index, &redo_pool, &redo_work, &redo_cls};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
@@ -2768,6 +2777,109 @@ extern "C" int kaiju_gpu_classify_batch_compact(kaiju_gpu_ctx *ctx, const kaiju_
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   KJ_HIP(hipMemcpyAsync(out, ctx->h_compact.p, (size_t)n_reads * sizeof(kaiju_gpu_compact), hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  return KAIJU_GPU_OK;
+  });
+}
+
+// ---- record extraction on the device (ingest.hip) ---------------------------------------------------------------
+static int no_ingest() {
+  if (!kj_ingest_launch) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "this library was linked without ingest.hip");
+  return KAIJU_GPU_OK;
+}
+static int no_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_parse_block_device(kaiju_gpu_ctx *ctx, const void *d_text1, uint64_t bytes1, const void *d_text2, uint64_t bytes2,
+                                            int fastq, int keep_names, uint32_t rec_cap, void *d_seqs, uint64_t *d_off,
+                                            kaiju_gpu_name_span *d_names, kaiju_gpu_parse_info *d_info, void *stream) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_ingest()) return rc;
+  if (!ctx) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  const char *err = "";
+  const int rc = kj_ingest_launch(&ctx->ingest, stream ? static_cast<hipStream_t>(stream) : ctx->stream, d_text1, bytes1, d_text2, bytes2,
+                                  fastq, keep_names, rec_cap, d_seqs, d_off, d_names, d_info, &err);
+  return rc ? fail(rc, err) : KAIJU_GPU_OK;
+  });
+}
+
+// text up, the passes queued on the context's stream, *info back (blocks until it is there); the other results stay in
+// ctx->h_seqs / h_off / ing_names
+static int parse_host_text(kaiju_gpu_ctx *ctx, const char *text1, uint64_t bytes1, const char *text2, uint64_t bytes2, int fastq,
+                           int keep_names, uint32_t rec_cap, kaiju_gpu_parse_info *info) {
+  if (!ctx || !info || (!text1 && bytes1) || (!text2 && bytes2)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (bytes1 > kji::kMaxBytes || bytes2 > kji::kMaxBytes) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 bytes");
+  if (int rc0 = no_ingest()) return rc0;
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  int rc;
+  if ((rc = ensure(ctx->ing_text1, bytes1 + 64))) return rc;
+  if (text2 && (rc = ensure(ctx->ing_text2, bytes2 + 64))) return rc;
+  if ((rc = ensure(ctx->h_seqs, bytes1 + bytes2 + 64))) return rc;
+  if ((rc = ensure(ctx->h_off, (2 * (size_t)rec_cap + 1) * 8))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)rec_cap + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->ing_info, sizeof(kaiju_gpu_parse_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
+  if (bytes2) KJ_HIP(hipMemcpyAsync(ctx->ing_text2.p, text2, bytes2, hipMemcpyHostToDevice, s));
+  const char *err = "";
+  rc = kj_ingest_launch(&ctx->ingest, s, ctx->ing_text1.p, bytes1, text2 ? ctx->ing_text2.p : nullptr, bytes2, fastq, keep_names, rec_cap,
+                        ctx->h_seqs.p, static_cast<uint64_t *>(ctx->h_off.p), static_cast<kaiju_gpu_name_span *>(ctx->ing_names.p),
+                        static_cast<kaiju_gpu_parse_info *>(ctx->ing_info.p), &err);
+  if (rc) return fail(rc, err);
+  KJ_HIP(hipMemcpyAsync(info, ctx->ing_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  return KAIJU_GPU_OK;
+}
+static uint32_t reads_emitted(const kaiju_gpu_parse_info &info, bool paired, uint32_t rec_cap) {
+  return std::min(rec_cap, paired ? std::min(info.n_records, info.n_records2) : info.n_records);
+}
+
+extern "C" int kaiju_gpu_parse_block(kaiju_gpu_ctx *ctx, const char *text1, uint64_t bytes1, const char *text2, uint64_t bytes2, int fastq,
+                                     int keep_names, uint32_t rec_cap, char *seqs, uint64_t *off, kaiju_gpu_name_span *names,
+                                     kaiju_gpu_parse_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (!off || (!names && rec_cap) || (!seqs && bytes1 + bytes2)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info)) return rc;
+  const uint32_t n = reads_emitted(*info, text2 != nullptr, rec_cap);
+  hipStream_t s = ctx->stream;
+  if (info->seq_bytes) KJ_HIP(hipMemcpyAsync(seqs, ctx->h_seqs.p, info->seq_bytes, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipMemcpyAsync(off, ctx->h_off.p, (2 * (size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (n) KJ_HIP(hipMemcpyAsync(names, ctx->ing_names.p, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  return KAIJU_GPU_OK;
+  });
+}
+
+extern "C" int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
+                                               const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
+                                               kaiju_gpu_compact *out, uint64_t *off, kaiju_gpu_name_span *names,
+                                               kaiju_gpu_parse_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (!ctx || !t || !off || (!names && rec_cap) || (!out && rec_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
+  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info)) return rc;
+  if (info->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
+  const bool paired = text2 != nullptr;
+  const uint32_t n = reads_emitted(*info, paired, rec_cap);
+  hipStream_t s = ctx->stream;
+  KJ_HIP(hipMemcpyAsync(off, ctx->h_off.p, (2 * (size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (n == 0) { KJ_HIP(hipStreamSynchronize(s)); return KAIJU_GPU_OK; }
+  KJ_HIP(hipMemcpyAsync(names, ctx->ing_names.p, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyDeviceToHost, s));
+  int rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info->max_mate_len));
+  if (rc) return rc;
+  if ((rc = ensure(ctx->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
+  if ((rc = ensure(ctx->h_compact, (size_t)n * sizeof(kaiju_gpu_compact)))) return rc;
+  rc = kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), n, paired ? 1 : 0,
+                                               static_cast<kaiju_gpu_hit *>(ctx->h_hits.p), static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), s);
+  if (rc) return rc;
+  KJ_HIP(hipMemcpyAsync(out, ctx->h_compact.p, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));
   return KAIJU_GPU_OK;
   });

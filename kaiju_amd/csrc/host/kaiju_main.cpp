@@ -582,7 +582,13 @@ struct Batch {
   HugeVec<uint64_t> off{0};
   CharVec names;                           // concatenated
   HugeVec<uint32_t> name_off{0};
-  size_t n() const { return name_off.size() - 1; }
+  // KAIJU_GPU_INGEST=device: the raw text of the batch instead of seqs / names; the records are found on the device
+  // (kaiju_gpu_classify_text_compact) and the names are spans into raw_a, which therefore lives as long as the batch
+  std::unique_ptr<RawBlock> raw_a, raw_b;
+  HugeVec<kaiju_gpu_name_span> nspans;
+  size_t n() const { return raw_a ? nspans.size() : name_off.size() - 1; }
+  const char *name_ptr(size_t r) const { return raw_a ? raw_a->text + nspans[r].pos : names.data() + name_off[r]; }
+  size_t name_len(size_t r) const { return raw_a ? nspans[r].len : name_off[r + 1] - name_off[r]; }
   // results
   HugeVec<kaiju_gpu_hit> hits;             // -v only
   HugeVec<kaiju_gpu_verbose> vrec;         // -v only: columns 6/7
@@ -598,6 +604,7 @@ struct Batch {
   void reset() {                           // empty, capacities kept
     seqs.clear(); off.assign(1, 0); names.clear(); name_off.assign(1, 0);
     hits.clear(); vrec.clear(); vtext.clear(); vpos.clear(); compact.clear(); text.clear();
+    raw_a.reset(); raw_b.reset(); nspans.clear();
   }
 };
 
@@ -853,6 +860,10 @@ int main(int argc, char **argv) {
   if (xmode && nodes_fn.empty()) nodes_fn = "-";
   // developer/test switch: run the ingest stages only and print "name<TAB>mate1<TAB>mate2" per read
   const bool parse_only = getenv("KAIJU_GPU_PARSE_ONLY") != nullptr;
+  // KAIJU_GPU_INGEST=device: stage 2 hands the raw blocks on and the device finds the records (ingest.hip).  Only where the
+  // 16-byte records are the output: ignored with -v, for kaijux / kaijup and with KAIJU_GPU_PARSE_ONLY.  Anything else: host.
+  const char *ingest_env = getenv("KAIJU_GPU_INGEST");
+  const bool device_ingest = ingest_env && !strcmp(ingest_env, "device") && !verbose && !xmode && !parse_only;
   if (verbose) fprintf(stderr, "%s Reading database\n", now().c_str());
   // Which GPUs: KAIJU_GPU_DEVICE=<n> (one, default 0) or KAIJU_GPU_DEVICES=<n,n,...|all>: the index is replicated on each of
   // them (parsed and packed once), input block b goes to context b mod (2 x GPUs) - SURVEY 8e's "block b to GPU b mod N" -
@@ -1038,9 +1049,14 @@ int main(int argc, char **argv) {
         for (;;) {
           std::unique_ptr<Batch> b = pool.get();               // (first the batch, then the block: see BatchPool)
           if (!q_raw.take_any(seq, pr)) { pool.put(std::move(b)); break; }
-          { StageTimer tm(g_ns_parse); pr.a->gather(); if (pr.b) pr.b->gather(); parse_blocks(*pr.a, pr.b.get(), in1_fn, in2_fn, *b); }
-          if (paired && pr.b->n_records > pr.a->n_records)
-            fprintf(stderr, "Warning: File %s has more reads then file %s\n", in2_fn.c_str(), in1_fn.c_str());
+          const bool more2 = paired && pr.b->n_records > pr.a->n_records;
+          {
+            StageTimer tm(g_ns_parse);
+            pr.a->gather(); if (pr.b) pr.b->gather();
+            if (device_ingest) { b->raw_a = std::move(pr.a); b->raw_b = std::move(pr.b); }
+            else parse_blocks(*pr.a, pr.b.get(), in1_fn, in2_fn, *b);
+          }
+          if (more2) fprintf(stderr, "Warning: File %s has more reads then file %s\n", in2_fn.c_str(), in1_fn.c_str());
           q_parsed.put(seq, std::move(b));
         }
       });
@@ -1051,7 +1067,7 @@ int main(int argc, char **argv) {
       gpu_threads.emplace_back([&, k] {
         std::unique_ptr<Batch> b;
         for (uint64_t seq = (uint64_t)k; q_parsed.take(seq, b); seq += n_ctx) {
-          const uint32_t n = (uint32_t)b->n();
+          uint32_t n = (uint32_t)b->n();
           int r = 0;
           if (parse_only) { q_done.put(seq, std::move(b)); continue; }
           wait_for_gpu();
@@ -1099,6 +1115,25 @@ int main(int argc, char **argv) {
           } else if (xmode) {
             b->hits.resize(n);
             r = kaiju_gpu_classify_batch(ctx[k], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, b->hits.data());
+          } else if (b->raw_a) {
+            const RawBlock &ra = *b->raw_a;
+            const RawBlock *rb = b->raw_b.get();
+            const uint32_t cap = ra.n_records;
+            b->compact.resize(cap); b->off.resize(2 * (size_t)cap + 1); b->nspans.resize(cap);
+            kaiju_gpu_parse_info pi;
+            memset(&pi, 0, sizeof pi);
+            r = kaiju_gpu_classify_text_compact(ctx[k], dtaxes[(size_t)(k / 2)], ra.text, ra.size, rb ? (rb->text ? rb->text : "") : nullptr,
+                                                rb ? rb->size : 0, ra.fastq ? 1 : 0, 0, cap, b->compact.data(), b->off.data(), b->nspans.data(), &pi);
+            if (r == 0) {
+              // the reader and the device must agree on the records of a block: anything else is a bug in one of them
+              if (pi.n_records != ra.n_records || (rb && pi.n_records2 != rb->n_records))
+                die("internal error: the device found " + std::to_string(pi.n_records) + " / " + std::to_string(pi.n_records2) + " records in a block, the reader " +
+                    std::to_string(ra.n_records) + " / " + std::to_string(rb ? rb->n_records : 0));
+              if (rb && pi.n_records2 < pi.n_records) die("File " + in1_fn + " contains more reads then file " + in2_fn);
+              if (pi.name_mismatch != ~0u)
+                die("Read names are not identical between the two input files. Probably reads are not in the same order in both files.");
+              n = cap;
+            }
           } else {
             b->compact.resize(n);
             r = kaiju_gpu_classify_batch_compact(ctx[k], dtaxes[(size_t)(k / 2)], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, b->compact.data());
@@ -1183,10 +1218,10 @@ int main(int argc, char **argv) {
           else kaiju_finalize_compact(&params, info.db_length, b->compact.data(), b->off.data(), n, paired ? 1 : 0, res.data());
           std::string &text = b->text;
           text.clear();
-          text.reserve((size_t)n * 24 + b->names.size());
+          text.reserve((size_t)n * 24 + (b->raw_a ? (size_t)n * 24 : b->names.size()));
           for (uint32_t r = 0; r < n; r++) {
-            const char *nm = b->names.data() + b->name_off[r];
-            const size_t nl = b->name_off[r + 1] - b->name_off[r];
+            const char *nm = b->name_ptr(r);
+            const size_t nl = b->name_len(r);
             if (res[r].classified) {
               text += "C\t"; text.append(nm, nl); text += '\t';
               append_u64(text, res[r].taxon);
