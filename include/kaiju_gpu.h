@@ -418,6 +418,50 @@ int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy
                                     kaiju_gpu_compact *out, uint64_t *off, kaiju_gpu_name_span *names,
                                     kaiju_gpu_parse_info *info);
 
+/* ---- the output lines on the device: 16-byte records in, text out ----------------------------------------- */
+/* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi without -v, as HIP passes
+   (kaiju_amd/csrc/format.hip; the rules: kj_format.h): per record the decision of kaiju_finalize_compact (E-value gate
+   included, bit for bit: the table argument is in kj_format.h) and the line "C\t<name>\t<taxon>\n" or "U\t<name>\t0\n", the
+   name being text1[names[r].pos, + names[r].len); the lines of records 0 .. n - 1 follow each other in `out`.  Mode,
+   use_evalue, min_evalue and input_is_protein are the context's, db_length its index's.  -v, kaijux and kaijup lines are not
+   made here. */
+typedef struct kaiju_gpu_format_info {
+  uint64_t text_bytes;             /* size of the whole text, whether or not it fitted                                      */
+  uint32_t n_records, n_classified;/* records formatted (= n), 'C' lines among them                                         */
+  uint32_t overflow;               /* 1: text_bytes > out_cap; the whole lines that fit are written, no byte at or behind   */
+                                   /* out_cap is touched                                                                    */
+  uint32_t n_inexact;              /* (the reserved word) records whose info carries KAIJU_HIT_INEXACT: they are formatted   */
+                                   /* like any other, a caller that must not print such lines looks here                    */
+} kaiju_gpu_format_info;
+/* All pointers are device pointers on the context's GPU; d_out must be 16-byte aligned (KAIJU_GPU_ERR_ARG otherwise), text 1
+   below 2^32 - 32 bytes.  d_recs: n records, d_off: 2n + 1 (as given to the classification), d_names: n.  Asynchronous on
+   `stream` (NULL: the context's own); nothing waits for the host.  The scratch - 20 bytes per record - lives in the context
+   and grows when a call needs more. */
+int kaiju_gpu_format_compact_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
+                                    const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names, void *d_out,
+                                    uint64_t out_cap, kaiju_gpu_format_info *d_info, void *stream);
+/* The same with host pointers (records, text and names up; *info and the bytes written down); blocks.  out[0 .. out_cap):
+   only the bytes of the lines written change. */
+int kaiju_gpu_format_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, int paired,
+                             const char *text1, uint64_t bytes1, const kaiju_gpu_name_span *names, char *out, uint64_t out_cap,
+                             kaiju_gpu_format_info *info);
+/* Host only: an out_cap that cannot overflow for n records whose names are disjoint pieces of a text of bytes1 bytes
+   (a line is its name and at most 24 bytes more): bytes1 + 24 * n */
+uint64_t kaiju_gpu_format_bound(uint64_t bytes1, uint32_t n);
+/* Host only: the table of the E-value gate as the library builds it for its contexts, pow(2, -bitscore(best)) for best <
+   n_out (at most 4096 entries are written).  Returns 0, or KAIJU_GPU_ERR_UNSUPPORTED when a score beyond the table has a
+   factor other than +0.0 on this host (the format entry points refuse to run then). */
+int kaiju_gpu_format_evalue_table(double *out, uint32_t n_out);
+/* Text in, text out: upload, the passes of kaiju_gpu_classify_text_compact and the passes above on one stream; what comes back
+   is *info_parse (read back in front of the classification, as there), *info_format and exactly info_format->text_bytes bytes
+   of out_text.  The stops of kaiju_gpu_classify_text_compact stay: info_parse->overflow is KAIJU_GPU_ERR_ARG with nothing
+   classified, a name mismatch or a shorter second text is reported in *info_parse and left to the caller.  out_cap below
+   the text's size (kaiju_gpu_format_bound(bytes1, rec_cap) never is): KAIJU_GPU_ERR_ARG, *info_format says what is needed. */
+int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
+                                    const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
+                                    char *out_text, uint64_t out_cap, kaiju_gpu_parse_info *info_parse,
+                                    kaiju_gpu_format_info *info_format);
+
 /* ---- several processes of a node, one per GPU: the gather --------------- */
 /* BASELINE north star: "reads shard embarrassingly across the GPUs of one node with the index replicated per GPU and per-GPU
    hit lists gathered with a single RCCL gather over xGMI".  The reference has no exchange (its threads append to one output

@@ -73,7 +73,9 @@ NAME_SPAN_DTYPE = np.dtype([("pos", "<u4"), ("len", "<u4")])                    
 PARSE_INFO_DTYPE = np.dtype([("n_records", "<u4"), ("n_records2", "<u4"), ("max_mate_len", "<u4"), ("name_mismatch", "<u4"),
                              ("seq_bytes", "<u8"), ("overflow", "<u4"), ("reserved", "<u4")])  # kaiju_gpu_parse_info
 NO_MISMATCH = 0xffffffff
-assert NAME_SPAN_DTYPE.itemsize == 8 and PARSE_INFO_DTYPE.itemsize == 32
+FORMAT_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"), ("n_classified", "<u4"), ("overflow", "<u4"),
+                              ("n_inexact", "<u4")])                                           # kaiju_gpu_format_info
+assert NAME_SPAN_DTYPE.itemsize == 8 and PARSE_INFO_DTYPE.itemsize == 32 and FORMAT_INFO_DTYPE.itemsize == 24
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -137,6 +139,15 @@ def lib():
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kaiju_gpu_classify_text_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kaiju_gpu_format_compact_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.kaiju_gpu_format_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.c_void_p]
+    L.kaiju_gpu_format_bound.restype = C.c_uint64
+    L.kaiju_gpu_format_bound.argtypes = [C.c_uint64, C.c_uint32]
+    L.kaiju_gpu_format_evalue_table.argtypes = [C.c_void_p, C.c_uint32]
+    L.kaiju_gpu_classify_text_to_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                                  C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -501,6 +512,45 @@ class Classifier:
                                 names.data_ptr(), info.data_ptr(), fastq=fastq, keep_names=keep_names, stream=stream)
         return {"seqs": seqs, "off": off, "names": names, "info": info}
 
+    def format_compact(self, recs: np.ndarray, off: np.ndarray, text1, names: np.ndarray, paired=False, out_cap=None, out=None):
+        """16-byte records, off[], the text the names lie in and the name spans (NAME_SPAN_DTYPE) to the lines of the output
+        file (kaiju_gpu_format_compact): host buffers, blocking.  Returns (out, info): out is a uint8 array of out_cap bytes
+        (default: kaiju_gpu_format_bound) of which the lines written have changed, info a FORMAT_INFO_DTYPE record."""
+        recs = np.ascontiguousarray(recs, dtype=COMPACT_DTYPE)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        t1 = np.frombuffer(bytes(text1) + b"\0", dtype=np.uint8) if not isinstance(text1, np.ndarray) else np.concatenate([text1, np.zeros(1, dtype=np.uint8)])
+        n = len(recs)
+        assert len(off) == 2 * n + 1 and len(names) == n
+        cap = int(out_cap) if out_cap is not None else format_bound(len(t1) - 1, n)
+        if out is None:
+            out = np.zeros(cap + 1, dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) >= cap
+        info = np.zeros(1, dtype=FORMAT_INFO_DTYPE)
+        _check(lib().kaiju_gpu_format_compact(self._h, recs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, t1.ctypes.data, len(t1) - 1,
+                                              names.ctypes.data, out.ctypes.data, cap, info.ctypes.data))
+        return out, info[0]
+
+    def format_compact_device(self, d_recs_ptr: int, d_off_ptr: int, n: int, d_text1_ptr: int, bytes1: int, d_names_ptr: int, d_out_ptr: int,
+                              out_cap: int, d_info_ptr: int, paired=False, stream: int = 0):
+        """the same for device-resident buffers (raw pointers; d_out 16-byte aligned): kaiju_gpu_format_compact_device,
+        asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_format_compact_device(self._h, d_recs_ptr or None, d_off_ptr or None, n, 1 if paired else 0, d_text1_ptr or None,
+                                                     bytes1, d_names_ptr or None, d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def classify_text_to_text(self, dtax: "DeviceTaxonomy", text1, text2=None, fastq=True, keep_names=False, rec_cap=None, out_cap=None):
+        """FASTQ / FASTA text in, the lines of the output file out (kaiju_gpu_classify_text_to_text).  Returns a dict: text
+        (bytes), info (PARSE_INFO_DTYPE record), format_info (FORMAT_INFO_DTYPE record)."""
+        t1, t2, cap = _text_args(text1, text2, rec_cap)
+        ocap = int(out_cap) if out_cap is not None else format_bound(len(t1) - 1, cap)
+        out = np.zeros(ocap + 1, dtype=np.uint8)
+        info = np.zeros(1, dtype=PARSE_INFO_DTYPE)
+        finfo = np.zeros(1, dtype=FORMAT_INFO_DTYPE)
+        _check(lib().kaiju_gpu_classify_text_to_text(self._h, dtax._h, t1.ctypes.data, len(t1) - 1, t2.ctypes.data if t2 is not None else None,
+                                                     len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
+                                                     out.ctypes.data, ocap, info.ctypes.data, finfo.ctypes.data))
+        return {"text": out[: int(finfo[0]["text_bytes"])].tobytes(), "info": info[0], "format_info": finfo[0]}
+
     OP_COUNT_NAMES = ("kmer_lookups", "update_si", "update_si_lines", "lf_steps", "lf_lines", "sa_samples", "read_meta",
                       "frag_desc", "window_fills", "term_searches", "si_spills", "hits", "multi_letter_steps", "items_read",
                       "matches_read", "items_written", "matches_written", "wave_iterations", "lane_iterations", "record_bytes", "pruned_chains", "window_lines")
@@ -574,6 +624,11 @@ def _text_args(text1, text2, rec_cap):
     t2 = arr(text2) if text2 is not None else None
     cap = int(rec_cap) if rec_cap is not None else int(np.count_nonzero(t1[:-1] == 10)) + 1
     return t1, t2, cap
+
+
+def format_bound(bytes1: int, n: int) -> int:
+    """an out_cap that cannot overflow for n records whose names are disjoint pieces of a text of bytes1 bytes"""
+    return int(lib().kaiju_gpu_format_bound(bytes1, n))
 
 
 def _reads_emitted(info, paired, cap):

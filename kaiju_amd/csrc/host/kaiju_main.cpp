@@ -601,10 +601,11 @@ struct Batch {
   const char *vtext_of(size_t r) const { return vtext.data() + vpos[r]; }
   HugeVec<kaiju_gpu_compact> compact;
   std::string text;
+  bool text_done = false;                  // KAIJU_GPU_OUTPUT=device: text came from the device, stage 4 passes it through
   void reset() {                           // empty, capacities kept
     seqs.clear(); off.assign(1, 0); names.clear(); name_off.assign(1, 0);
     hits.clear(); vrec.clear(); vtext.clear(); vpos.clear(); compact.clear(); text.clear();
-    raw_a.reset(); raw_b.reset(); nspans.clear();
+    raw_a.reset(); raw_b.reset(); nspans.clear(); text_done = false;
   }
 };
 
@@ -864,6 +865,12 @@ int main(int argc, char **argv) {
   // 16-byte records are the output: ignored with -v, for kaijux / kaijup and with KAIJU_GPU_PARSE_ONLY.  Anything else: host.
   const char *ingest_env = getenv("KAIJU_GPU_INGEST");
   const bool device_ingest = ingest_env && !strcmp(ingest_env, "device") && !verbose && !xmode && !parse_only;
+  // KAIJU_GPU_OUTPUT=device: the device also writes the lines (format.hip) and the batch comes back as finished text.  Only
+  // where device ingest is honoured - the names lie in the raw block on the device - so never with -v or for kaijux / kaijup.
+  const char *output_env = getenv("KAIJU_GPU_OUTPUT");
+  const bool device_output = output_env && !strcmp(output_env, "device") && device_ingest;
+  if (output_env && !strcmp(output_env, "device") && !device_output)
+    fprintf(stderr, "KAIJU_GPU_OUTPUT=device is ignored: it needs KAIJU_GPU_INGEST=device and the three-column output of kaiju / kaiju-multi without -v\n");
   if (verbose) fprintf(stderr, "%s Reading database\n", now().c_str());
   // Which GPUs: KAIJU_GPU_DEVICE=<n> (one, default 0) or KAIJU_GPU_DEVICES=<n,n,...|all>: the index is replicated on each of
   // them (parsed and packed once), input block b goes to context b mod (2 x GPUs) - SURVEY 8e's "block b to GPU b mod N" -
@@ -1074,6 +1081,7 @@ int main(int argc, char **argv) {
           StageTimer tm(g_ns_gpu);
           wall_mark("gpu call begins, batch", (long long)seq);
           uint64_t piece_error_flags = 0;
+          uint64_t device_inexact = 0;
           if (verbose) {
             b->hits.resize(n);
             b->vrec.resize(n);
@@ -1115,6 +1123,32 @@ int main(int argc, char **argv) {
           } else if (xmode) {
             b->hits.resize(n);
             r = kaiju_gpu_classify_batch(ctx[k], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, b->hits.data());
+          } else if (b->raw_a && device_output) {
+            // raw text in, the lines out: one upload, the read-back of the counts, one download (kaiju_gpu_classify_text_to_text)
+            const RawBlock &ra = *b->raw_a;
+            const RawBlock *rb = b->raw_b.get();
+            const uint32_t cap = ra.n_records;
+            const uint64_t out_cap = kaiju_gpu_format_bound(ra.size, cap);
+            b->text.resize(out_cap);
+            kaiju_gpu_parse_info pi;
+            kaiju_gpu_format_info fi;
+            memset(&pi, 0, sizeof pi);
+            memset(&fi, 0, sizeof fi);
+            r = kaiju_gpu_classify_text_to_text(ctx[k], dtaxes[(size_t)(k / 2)], ra.text, ra.size, rb ? (rb->text ? rb->text : "") : nullptr,
+                                                rb ? rb->size : 0, ra.fastq ? 1 : 0, 0, cap, &b->text[0], out_cap, &pi, &fi);
+            if (r == 0) {
+              if (pi.n_records != ra.n_records || (rb && pi.n_records2 != rb->n_records))
+                die("internal error: the device found " + std::to_string(pi.n_records) + " / " + std::to_string(pi.n_records2) + " records in a block, the reader " +
+                    std::to_string(ra.n_records) + " / " + std::to_string(rb ? rb->n_records : 0));
+              if (rb && pi.n_records2 < pi.n_records) die("File " + in1_fn + " contains more reads then file " + in2_fn);
+              if (pi.name_mismatch != ~0u)
+                die("Read names are not identical between the two input files. Probably reads are not in the same order in both files.");
+              if (fi.n_records != cap) die("internal error: the device formatted " + std::to_string(fi.n_records) + " records of " + std::to_string(cap));
+              b->text.resize(fi.text_bytes);
+              b->text_done = true;
+              device_inexact = fi.n_inexact;
+              n = 0;                                  // (no records came back: nothing to look through below)
+            }
           } else if (b->raw_a) {
             const RawBlock &ra = *b->raw_a;
             const RawBlock *rb = b->raw_b.get();
@@ -1146,7 +1180,7 @@ int main(int argc, char **argv) {
             uint64_t ni = 0;
             if (!b->hits.empty()) { for (uint32_t q = 0; q < n; q++) ni += (b->hits[q].flags & KAIJU_HIT_INEXACT) ? 1 : 0; }
             else for (uint32_t q = 0; q < n; q++) ni += (b->compact[q].info & KAIJU_HIT_INEXACT) ? 1 : 0;
-            if (ni) inexact_reads += ni;
+            if (ni + device_inexact) inexact_reads += ni + device_inexact;
           }
 
           wall_mark("gpu call done, batch", (long long)seq);
@@ -1176,6 +1210,7 @@ int main(int argc, char **argv) {
             q_text.put(seq, std::move(b));
             continue;
           }
+          if (b->text_done) { q_text.put(seq, std::move(b)); continue; }
           res.resize(n);
           if (xmode) {
             // E-value gate and C/U decision as for kaiju; the ids are sequence numbers: names in sequence order

@@ -21,13 +21,18 @@
 
 #include "../../include/kaiju_gpu.h"
 #include "kj_ingest.h"
+#include "kj_scan.h"
 
 using namespace kji;
+using kjs::OpAdd32;
+using kjs::OpAdd64;
+using kjs::block_scan_excl;     // (shared with format.hip)
 
 namespace {
 
 constexpr int kIngBlock = 256;
-static_assert(kIngBlock == (int)kTileLanes && kIngBlock == (int)kScanBlock, "one lane per chunk of a tile / element of a scan block");
+static_assert(kIngBlock == (int)kTileLanes && kIngBlock == (int)kScanBlock && kIngBlock == kjs::kScanLanes,
+              "one lane per chunk of a tile / element of a scan block");
 
 struct IngHdr { uint32_t n_lines, any_empty, first_nonempty, n_records; };
 struct IngShared { uint32_t max_mate_len, name_mismatch; };
@@ -57,31 +62,7 @@ struct IngRec {
   kaiju_gpu_parse_info *info;
 };
 
-struct OpAdd32 { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
-struct OpAdd64 { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; } };
 struct OpFq { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return fq_compose(a, b); } };
-
-// exclusive scan over the 256 lanes of a block in lane order (op need not commute); *total = all of them
-template <class T, class Op>
-__device__ T block_scan_excl(T v, T ident, T *total, Op op) {
-  __shared__ T wtot[kIngBlock / 64];
-  const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
-  T x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(x, d, 64);
-    if (lane >= d) x = op(y, x);
-  }
-  const T up = __shfl_up(x, 1, 64);
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  T pre = ident, tot = ident;
-#pragma unroll
-  for (int k = 0; k < kIngBlock / 64; k++) { if (k < w) pre = op(pre, wtot[k]); tot = op(tot, wtot[k]); }
-  __syncthreads();
-  *total = tot;
-  return lane ? op(pre, up) : pre;
-}
 
 __global__ void k_ing_init(IngHdr *h1, IngHdr *h2, IngShared *sh) {
   if (blockIdx.x || threadIdx.x) return;

@@ -16,6 +16,7 @@
 #include "../../include/kaiju_gpu.h"
 
 #include "taxonomy.h"
+#include "kj_format.h"
 
 extern "C" int kaiju_taxonomy_load(const char *path, kaiju_taxonomy **out) {
   if (!path || !out) return KAIJU_GPU_ERR_ARG;
@@ -179,4 +180,14 @@ extern "C" int kaiju_finalize_compact(const kaiju_gpu_params *p, double db_lengt
     if (h.lca > 0) { o.taxon = h.lca; o.classified = 1; }
   }
   return KAIJU_GPU_OK;
+}
+
+// The table of the E-value gate of the format passes (kj_format.h: pow_factor is the expression above).  It is built in this
+// file so that the compiler that translated kaiju_finalize_compact's pow translates the table's too.
+extern "C" int kaiju_gpu_format_evalue_table(double *out, uint32_t n_out) {
+  if (!out && n_out) return KAIJU_GPU_ERR_ARG;
+  std::vector<double> pw(kjf::kPowK);
+  const bool ok = kjf::build_pow_table(pw.data(), kjf::kPowK);
+  for (uint32_t b = 0; b < n_out && b < kjf::kPowK; b++) out[b] = pw[b];
+  return ok ? KAIJU_GPU_OK : KAIJU_GPU_ERR_UNSUPPORTED;
 }
