@@ -38,6 +38,7 @@
 #include "host_index.h"
 #include "host_tables.h"
 #include "kj_core.h"
+#include "kj_flow.h"
 #include "taxonomy.h"
 #include "exact_pass.h"
 #include "kj_ingest.h"
@@ -60,7 +61,6 @@ using namespace kj;
 // ----------------------------------------------------------------------------------------
 // kernels
 // ----------------------------------------------------------------------------------------
-constexpr int kBlock = 256;
 constexpr uint32_t kLocDeferRows = 8;     // k_mem_locate / k_mem_post1: reads whose matches hold more rows go to the many-rows instantiation
 
 __device__ __forceinline__ void load_tables(ConstTables &s_ct, const ConstTables *g_ct) {
@@ -73,7 +73,6 @@ __device__ __forceinline__ void load_tables(ConstTables &s_ct, const ConstTables
 // Stage 1, one lane per read, 64-thread blocks.  stage_bytes > 0: the six frame strings of every
 // lane are staged in LDS (dword-interleaved over the wavefront) and copied out with 16-byte
 // stores; 0: reads too long for LDS, strings are written in place.
-constexpr int kFragBlock = 64;
 __global__ void __launch_bounds__(kFragBlock)
 k_fragments(const ConstTables *__restrict__ g_ct, Params p, SegTables st, Batch b, SegQueue sq, uint32_t *err,
             uint32_t stage_bytes) {
@@ -2049,9 +2048,7 @@ extern "C" int kaiju_gpu_create(kaiju_gpu_ctx **out, const kaiju_gpu_index *ix, 
   if (p->mode == 0) KJ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mem, kBlock, 0));
   else {
     const bool g_wide = ix->dev.mb_base != nullptr;
-    const uint32_t g_k = g_wide ? ix->dev.kmer_k : ix->dev.kline_k;
-    c->greedy2 = ix->dev.blocks64 && (g_wide ? ix->dev.kmer64 != nullptr : ix->dev.kline != nullptr) && g_k >= 2 &&
-                 g_k <= p->seed_length && p->seed_length >= 3;
+    c->greedy2 = flow_greedy2(flow_index(ix->dev), p->seed_length);
     if (const char *e = getenv("KAIJU_GPU_GREEDY_LANE")) { if (!strcmp(e, "v1")) c->greedy2 = false; }
     // (the row-pool lane is parity-green but SLOWER than greedy_lane2 at the 480 rows a CU's LDS holds - DESIGN.md 6b, round 6:
     //  opt-in, KAIJU_GPU_GREEDY_LANE=v3)
@@ -2109,10 +2106,6 @@ extern "C" int kaiju_gpu_create(kaiju_gpu_ctx **out, const kaiju_gpu_index *ix, 
 
 extern "C" void kaiju_gpu_destroy(kaiju_gpu_ctx *ctx) { delete ctx; }
 
-// counters buffer layout (uint32): [0] main work counter, [1] retry work counter,
-// [2] retry list length, [3] stage-1 error flags
-// tax / d_compact: not null = the 16-byte records (LCA on the device) are written too - by the fused post-search pass where
-// that serves the configuration (k_mem_post1 / k_mem_post2), by k_lca behind everything else otherwise
 // the SEG pass over the fragments stage 1 (or k_segflag) queued
 static void launch_seg(const kaiju_gpu_ctx *c, hipStream_t s, const Params &p, const SegTables &st, const Batch &b, const SegQueue &sq) {
   const dim3 grid(c->n_cu * 32), blk(kSegBlock);
@@ -2123,14 +2116,60 @@ static void launch_seg(const kaiju_gpu_ctx *c, hipStream_t s, const Params &p, c
     default: hipLaunchKernelGGL(k_seg, grid, blk, 0, s, p, st, b, sq); break;
   }
 }
+// the plan (kj_flow.h) of a call of this context
+static FlowPlan plan_call(const kaiju_gpu_ctx *c, uint64_t seq_bytes, uint32_t n, int paired, uint32_t max_read_len, bool records16) {
+  FlowSwitches sw;
+  sw.p = c->kp;
+  sw.verbose = c->verbose; sw.verbose_v1 = c->verbose_v1; sw.mem_v1 = c->mem_v1; sw.stage1_old = c->stage1_old;
+  sw.stage1_lane = c->stage1_lane; sw.lazy_seg = c->lazy_seg; sw.fused_post = c->fused_post; sw.exact_pass = c->exact_pass;
+  sw.greedy2 = c->greedy2; sw.greedy3 = c->greedy3; sw.count_ops = c->count_ops; sw.blocks_retry = c->blocks_retry;
+  return plan_flow(flow_index(c->ix->dev), sw, FlowCall{n, paired != 0, max_read_len, seq_bytes, records16});
+}
+static int plan_status(const FlowPlan &plan) {
+  switch (plan.status) {
+    case FlowStatus::ProteinPaired: return fail(KAIJU_GPU_ERR_ARG, "protein input has no paired mode (kaiju.cpp:201)");
+    case FlowStatus::ProteinTooLong: return fail(KAIJU_GPU_ERR_UNSUPPORTED, "protein read longer than 2^28");
+    case FlowStatus::TooManyFragSlots: return fail(KAIJU_GPU_ERR_UNSUPPORTED, "batch too large: split it (fragment slots exceed 2^32)");
+    case FlowStatus::Ok: break;
+  }
+  return KAIJU_GPU_OK;
+}
+// the stage buffers of a batch, sized by the plan, and the SEG work list; hits: where the lanes write their records
+static int bind_batch(kaiju_gpu_ctx *c, const FlowPlan &plan, const void *d_seqs, const uint64_t *d_off, uint32_t n, int paired, void *hits,
+                      Batch &b, SegQueue &sq) {
+  int rc;
+  if ((rc = ensure(c->pep, plan.pep_bytes))) return rc;
+  if ((rc = ensure(c->frags, plan.n_frag_slots * sizeof(Frag)))) return rc;
+  if ((rc = ensure(c->meta, (size_t)n * sizeof(ReadMeta) + 16))) return rc;
+  if ((rc = ensure(c->counters, 4096))) return rc;     // exact_pass.h: CounterSlot
+  if ((rc = ensure(c->seg_items, plan.seg_cap * sizeof(SegWork)))) return rc;
+  if ((rc = ensure(c->seg_recs, plan.seg_cap * sizeof(SegRec)))) return rc;
+  b.seqs = static_cast<const uint8_t *>(d_seqs); b.off = d_off; b.n_reads = n; b.paired = paired ? 1 : 0;
+  b.pep = static_cast<uint8_t *>(c->pep.p); b.frags = static_cast<Frag *>(c->frags.p);
+  b.meta = static_cast<ReadMeta *>(c->meta.p); b.hits = static_cast<Hit *>(hits);
+  sq.items = static_cast<SegWork *>(c->seg_items.p); sq.recs = static_cast<SegRec *>(c->seg_recs.p);
+  sq.count = static_cast<uint32_t *>(c->counters.p) + kCntSegQueue; sq.cap = (uint32_t)plan.seg_cap;
+  return 0;
+}
 // the exact pass: reads its list holds, fragments of its queue, (left, right) pairs of its pool; SEG scratch of k_redo_seg
-// for fragments of up to max_frag residues (per block 4 * cap_ints ints and cls_bytes bytes)
+// for fragments of up to max_frag residues (per block 4 * cap_ints ints and cls_bytes bytes).  index_entries: fragments the
+// index of the pool is sized for
 constexpr uint32_t kRedoReads = 1u << 16, kRedoFrags = 1u << 18, kRedoPairs = 1u << 22;
-static void size_redo_seg(ExactPassLaunch &xp, uint64_t max_frag) {
+static int bind_exact_seg(kaiju_gpu_ctx *c, ExactPassLaunch &xp, uint64_t max_frag, uint64_t index_entries, const Batch &b, hipStream_t s) {
   xp.cap_ints = (uint32_t)(2 * max_frag + 4);
   xp.cls_bytes = (uint32_t)((max_frag + 64) & ~63ull);
   const uint64_t per_block = 16ull * xp.cap_ints + xp.cls_bytes;
   xp.seg_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (256ull << 20) / per_block));
+  int rc;
+  if ((rc = ensure(c->redo_index, (size_t)index_entries * sizeof(uint2)))) return rc;
+  if ((rc = ensure(c->redo_pool, (size_t)kRedoPairs * 8))) return rc;
+  if ((rc = ensure(c->redo_work, (size_t)xp.seg_blocks * 16 * xp.cap_ints))) return rc;
+  if ((rc = ensure(c->redo_cls, (size_t)xp.seg_blocks * xp.cls_bytes))) return rc;
+  uint32_t *cnt = static_cast<uint32_t *>(c->counters.p);
+  xp.st = c->ix->st; xp.b = b; xp.cnt = cnt; xp.stream = s;
+  xp.big = BigSeg{static_cast<uint2 *>(c->redo_index.p), static_cast<int32_t *>(c->redo_pool.p), cnt + kCntExactPairs, kRedoPairs};
+  xp.work = static_cast<int32_t *>(c->redo_work.p); xp.cls = static_cast<uint8_t *>(c->redo_cls.p);
+  return 0;
 }
 // KAIJU_GPU_CALL_TIMES=1: host-side marks of a classification call on stderr (ms since the first mark; which thread) - where a
 // call's wall time goes when it is not in the kernels (allocations of a context's first call, copies, waits)
@@ -2142,142 +2181,126 @@ static void call_mark(const char *what) {
   fprintf(stderr, "[call %8.1f ms, thread %04x] %s\n", ms, (unsigned)(std::hash<std::thread::id>()(std::this_thread::get_id()) & 0xffffu), what);
 }
 
+static void launch_stage1(const kaiju_gpu_ctx *c, hipStream_t s, const FlowPlan &plan, const Params &p, const Batch &b, const SegQueue &sq,
+                          uint32_t *err) {
+  const kaiju_gpu_index *ix = c->ix;
+  const uint32_t n = b.n_reads;
+  const dim3 grid_lane((n + kFragBlock - 1) / kFragBlock), grid_fast((n + kS1Block - 1) / kS1Block);
+  switch (plan.stage1) {
+    case FlowStage1::Protein:
+      hipLaunchKernelGGL(k_fragments_protein, grid_lane, dim3(kFragBlock), 0, s, ix->d_ct, p, ix->st, b, sq, err); break;
+    case FlowStage1::LongTrig:
+      hipLaunchKernelGGL((k_fragments_fast<true, kS1UnitsLong>), grid_fast, dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, err); break;
+    case FlowStage1::Long:
+      hipLaunchKernelGGL((k_fragments_fast<false, kS1UnitsLong>), grid_fast, dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, err); break;
+    case FlowStage1::FastTrig:
+      hipLaunchKernelGGL(k_fragments_fast<true>, grid_fast, dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, err); break;
+    case FlowStage1::Team:
+      hipLaunchKernelGGL(k_fragments_team, dim3((unsigned)((n + kS1TeamsPerBlock - 1) / kS1TeamsPerBlock)), dim3(kS1TeamBlock), 0, s,
+                         ix->d_s1, p, b, err);
+      break;
+    case FlowStage1::Fast:
+      hipLaunchKernelGGL(k_fragments_fast<false>, grid_fast, dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, err); break;
+    case FlowStage1::Old:
+      hipLaunchKernelGGL(k_fragments, grid_lane, dim3(kFragBlock), (size_t)plan.per_lane * kFragBlock, s, ix->d_ct, p, ix->st, b, sq, err,
+                         plan.per_lane);
+      break;
+  }
+}
+// The instantiation of a kernel that a run-time value picks: one place each
+static auto pick_mem_post1(bool records16) { return records16 ? k_mem_post1<true> : k_mem_post1<false>; }
+static auto pick_mem_post2(bool records16) { return records16 ? k_mem_post2<true> : k_mem_post2<false>; }
+static auto pick_mem_verbose(bool wide) { return wide ? k_mem_verbose<true> : k_mem_verbose<false>; }
+static auto pick_greedy_verbose(bool wide) { return wide ? k_mem_verbose<true, false> : k_mem_verbose<false, false>; }
+// the ids of the reads whose best matches wait in their records (MEM and Greedy); list_count: the counter of the mode's list of
+// reads whose matches hold many rows (k_mem_locate_list)
+static void launch_locate(const kaiju_gpu_ctx *c, hipStream_t s, FlowLocate how, const Params &p, const Batch &b, uint32_t *loc_list,
+                          uint32_t *list_count) {
+  const kaiju_gpu_index *ix = c->ix;
+  const dim3 grid_reads((b.n_reads + kBlock - 1) / kBlock);
+  const dim3 grid_team((unsigned)(((uint64_t)b.n_reads * kLocTeam + 255) / 256));          // k_mem_locate_wide / _team: kLocTeam lanes per read
+  switch (how) {
+    case FlowLocate::RowTax:
+      hipLaunchKernelGGL(k_mem_locate<false>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, list_count);
+      hipLaunchKernelGGL(k_mem_locate_list<false>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, list_count);
+      break;
+    case FlowLocate::RowTaxWide:
+      hipLaunchKernelGGL(k_mem_locate<true>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, list_count);
+      hipLaunchKernelGGL(k_mem_locate_list<true>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, list_count);
+      break;
+    case FlowLocate::Team: hipLaunchKernelGGL(k_mem_locate_team, grid_team, dim3(256), 0, s, ix->dev, p, b); break;
+    case FlowLocate::WideWalk: hipLaunchKernelGGL(k_mem_locate_wide, grid_team, dim3(256), 0, s, ix->dev, p, b); break;
+    case FlowLocate::InLane: case FlowLocate::Fused: break;
+  }
+}
+
+// Computes the plan of the call (kj_flow.h), then: buffers, argument structs, the launches the plan names.
+// tax / d_compact: not null = the 16-byte records (LCA on the device) are written too - by the fused post-search pass where
+// that serves the configuration (k_mem_post1 / k_mem_post2), by k_lca behind everything else otherwise
 static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes, const uint64_t *d_off,
                         uint32_t n, int paired, uint32_t max_read_len, kaiju_gpu_hit *d_out, hipStream_t s,
                         const kaiju_gpu_taxonomy *tax = nullptr, kaiju_gpu_compact *d_compact = nullptr) {
   const kaiju_gpu_index *ix = c->ix;
   const Params &p = c->kp;
-  if (max_read_len == 0) max_read_len = 1024;
-  const bool protein = (p.flags & kParamProtein) != 0;
-  if (protein) {
-    // a protein read is its own (single) frame: fragments are up to max_read_len long, not a third of it
-    if (paired) return fail(KAIJU_GPU_ERR_ARG, "protein input has no paired mode (kaiju.cpp:201)");
-    if (max_read_len > 0x10000000u) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "protein read longer than 2^28");
-    max_read_len *= 3;
-  }
-  const uint64_t max_pair = (uint64_t)max_read_len * (paired ? 2 : 1);
-  call_mark("launch_batch: begin");
-  // stage buffers
-  const uint64_t pep_bytes = 2 * seq_bytes + kPepPerRead * n + 32 + 256;   // pep_base() + window over-read slack
-  const uint64_t n_frag_slots = 2 * ((2 * seq_bytes) / (p.m + 1) + 7ull * n) + 8;
+  const FlowPlan plan = plan_call(c, seq_bytes, n, paired, max_read_len, tax != nullptr);
   int rc;
-  if ((rc = ensure(c->pep, pep_bytes))) return rc;
-  if ((rc = ensure(c->frags, n_frag_slots * sizeof(Frag)))) return rc;
-  if (n_frag_slots >= 0xffffffffull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "batch too large: split it (fragment slots exceed 2^32)");
-  if ((rc = ensure(c->meta, (size_t)n * sizeof(ReadMeta) + 16))) return rc;
-  if ((rc = ensure(c->counters, 4096))) return rc;     // [0, 256) counters, [512, ..) totals of the counting lanes
+  if ((rc = plan_status(plan))) return rc;
+  const uint64_t max_pair = plan.max_pair;
+  call_mark("launch_batch: begin");
+  Batch b;
+  SegQueue sq;
+  if ((rc = bind_batch(c, plan, d_seqs, d_off, n, paired, d_out, b, sq))) return rc;
   if ((rc = ensure(c->retry_list, (size_t)n * 4 + 16))) return rc;
   if ((rc = ensure(c->loc_list, (size_t)n * 4 + 16))) return rc;        // reads whose matches hold many rows (k_mem_locate_list)
   uint32_t *loc_list = static_cast<uint32_t *>(c->loc_list.p);
-  Batch b;
-  b.seqs = static_cast<const uint8_t *>(d_seqs); b.off = d_off; b.n_reads = n; b.paired = paired ? 1 : 0;
-  b.pep = static_cast<uint8_t *>(c->pep.p); b.frags = static_cast<Frag *>(c->frags.p);
-  b.meta = static_cast<ReadMeta *>(c->meta.p); b.hits = reinterpret_cast<Hit *>(d_out);
   uint32_t *cnt = static_cast<uint32_t *>(c->counters.p);
-  // SEG work list: at most one entry per original fragment
-  const uint64_t seg_cap = p.seg ? std::min<uint64_t>(n_frag_slots / 2 + 8, 0x00ffffffull) : 1;
-  if ((rc = ensure(c->seg_items, seg_cap * sizeof(SegWork)))) return rc;
-  if ((rc = ensure(c->seg_recs, seg_cap * sizeof(SegRec)))) return rc;
-  SegQueue sq;
-  sq.items = static_cast<SegWork *>(c->seg_items.p); sq.recs = static_cast<SegRec *>(c->seg_recs.p);
-  sq.count = cnt + 4; sq.cap = (uint32_t)seg_cap;
 #ifdef KJ_PROF
   KJ_HIP(hipMemsetAsync(cnt, 0, 4096, s));
 #else
-  KJ_HIP(hipMemsetAsync(cnt, 0, 1024, s));
+  KJ_HIP(hipMemsetAsync(cnt, 0, kCntProf * sizeof(uint32_t), s));
 #endif
   KJ_HIP(hipEventRecord(c->ev[0], s));
   const dim3 grid_reads((n + kBlock - 1) / kBlock), blk(kBlock);
-  bool fused = false;              // the records (and, with a taxonomy, the 16-byte records) are finished by k_mem_post1 / _post2
-  const dim3 grid_team((unsigned)(((uint64_t)n * kLocTeam + 255) / 256));          // k_mem_locate_wide / _team: kLocTeam lanes per read
-  // which stage 1 / SEG flow: the fast stage 1 serves mates up to kS1MaxLenLong nucleotides (two instantiations); in MEM mode on the second-generation
-  // lanes SEG is then looked at lazily (kj_core.h: kParamLazySeg), everywhere else stage 1 detects the SEG trigger itself
-  const bool mem_narrow2 = ix->dev.blocks64 && ix->dev.kline && ix->dev.kline_k >= 2 && ix->dev.kline_k <= p.m;
-  const bool mem_wide2 = ix->dev.blocks64 && ix->dev.mb_base && ix->dev.kmer64 && ix->dev.kmer_k >= 2 && ix->dev.kmer_k <= p.m;
-  // kaiju -v in MEM mode: the VERBOSE instantiations of those lanes + k_mem_verbose - where a match's place in its read fits the
-  // 16 + 16 bits of the lanes' notes (reads of 196 000 nt and more: the first-generation lanes, which also serve -v in Greedy
-  // mode, the retry pass and the exact pass)
-  const bool vb_v2 = c->verbose && !c->verbose_v1 && max_read_len / 3 + 4 < 65536 && 2 * max_pair / (p.m + 1) + 8 < 65536;
-  const bool mem_v2 = p.mode == 0 && (mem_narrow2 || mem_wide2) && !c->mem_v1 && (!c->verbose || vb_v2);
-  const bool fast1 = !protein && !c->stage1_old && max_read_len <= kS1MaxLenLong && p.m >= 1 && p.m <= 64;
-  const bool long1 = max_read_len > kS1MaxLen;              // (192 .. 287 nt: the instantiation with six units per frame string)
-  const bool lazy = fast1 && mem_v2 && p.seg && c->lazy_seg;
-  const bool trig1 = fast1 && p.seg && !lazy;
-  // the fused post-search pass (k_mem_post1 / _post2): narrow MEM lanes with the row -> taxon table, SEG lazily or not at all
-  // (an eager SEG pass may send ANY read to the exact pass: nothing is final before that)
-  fused = p.mode == 0 && mem_v2 && mem_narrow2 && ix->dev.row_tax && (lazy || !p.seg) && c->fused_post && n > 0 && !c->verbose;
-  // unused id slots read as 0.  Not with the 16-byte records as the output on the fused path: the lanes write the header of every
-  // record and the entries they announce in it, k_mem_post1 / _post2 read nothing else - d_hits is scratch there (1.84 GB less to
-  // write per 10 M reads)
-  if (n > 0 && !(fused && tax)) KJ_HIP(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(kaiju_gpu_hit), s));
-  if (n > 0) {
-    // LDS staging area per lane: all frame strings of a read (or pair), rounded to 16 bytes
-    uint32_t per_lane = (uint32_t)((2 * max_pair + 12 + 15) & ~15ull);
-    if ((uint64_t)per_lane * kFragBlock > 60000) per_lane = 0;        // long reads: write in place
-    if (protein)
-      hipLaunchKernelGGL(k_fragments_protein, dim3((n + kFragBlock - 1) / kFragBlock), dim3(kFragBlock), 0, s,
-                         ix->d_ct, p, ix->st, b, sq, cnt + 3);
-    else if (fast1 && trig1 && long1)
-      hipLaunchKernelGGL((k_fragments_fast<true, kS1UnitsLong>), dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
-    else if (fast1 && long1)
-      hipLaunchKernelGGL((k_fragments_fast<false, kS1UnitsLong>), dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
-    else if (fast1 && trig1)
-      hipLaunchKernelGGL(k_fragments_fast<true>, dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
-    else if (fast1 && !c->stage1_lane && !paired)     // (pairs: the team kernel was slower)
-      hipLaunchKernelGGL(k_fragments_team, dim3((unsigned)((n + kS1TeamsPerBlock - 1) / kS1TeamsPerBlock)), dim3(kS1TeamBlock), 0, s,
-                         ix->d_s1, p, b, cnt + 3);
-    else if (fast1)
-      hipLaunchKernelGGL(k_fragments_fast<false>, dim3((n + kS1Block - 1) / kS1Block), dim3(kS1Block), 0, s, ix->d_s1, p, b, sq, cnt + 3);
-    else
-      hipLaunchKernelGGL(k_fragments, dim3((n + kFragBlock - 1) / kFragBlock), dim3(kFragBlock),
-                         (size_t)per_lane * kFragBlock, s, ix->d_ct, p, ix->st, b, sq, cnt + 3, per_lane);
+  const bool lazy = plan.seg == FlowSeg::Lazy;
+  if (plan.clear_out) KJ_HIP(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(kaiju_gpu_hit), s));
+  if (plan.run) {
+    launch_stage1(c, s, plan, p, b, sq, cnt + kCntErrFlags);
     KJ_HIP(hipGetLastError());
   }
   KJ_HIP(hipEventRecord(c->ev[1], s));
-  if (n > 0 && p.seg && !lazy) {
+  if (plan.run && plan.seg == FlowSeg::Eager) {
     launch_seg(c, s, p, ix->st, b, sq);
     KJ_HIP(hipGetLastError());
-    if (p.mode == 0) {
-      hipLaunchKernelGGL(k_seg_apply, grid_reads, blk, 0, s, ix->d_ct, p, b, sq, cnt + 3);
+    if (plan.seg_apply) {
+      hipLaunchKernelGGL(k_seg_apply, grid_reads, blk, 0, s, ix->d_ct, p, b, sq, cnt + kCntErrFlags);
       KJ_HIP(hipGetLastError());
     }
   }
   KJ_HIP(hipEventRecord(c->ev[2], s));
   WorkList wl_main;
-  wl_main.counter = cnt + 0; wl_main.reads = nullptr; wl_main.n_items_ptr = nullptr; wl_main.n_items = n;
-  wl_main.retry_list = static_cast<uint32_t *>(c->retry_list.p); wl_main.retry_count = cnt + 2;
+  wl_main.counter = cnt + kCntMainWork; wl_main.reads = nullptr; wl_main.n_items_ptr = nullptr; wl_main.n_items = n;
+  wl_main.retry_list = static_cast<uint32_t *>(c->retry_list.p); wl_main.retry_count = cnt + kCntRetryLen;
   WorkList wl_retry;
-  wl_retry.counter = cnt + 1; wl_retry.reads = static_cast<const uint32_t *>(c->retry_list.p);
-  wl_retry.n_items_ptr = cnt + 2; wl_retry.n_items = 0; wl_retry.retry_list = nullptr; wl_retry.retry_count = nullptr;
+  wl_retry.counter = cnt + kCntRetryWork; wl_retry.reads = static_cast<const uint32_t *>(c->retry_list.p);
+  wl_retry.n_items_ptr = cnt + kCntRetryLen; wl_retry.n_items = 0; wl_retry.retry_list = nullptr; wl_retry.retry_count = nullptr;
   const uint64_t lanes_main = (uint64_t)c->blocks_main * kBlock;
-  // the exact pass (kj_core.h: BigSeg; kernels in exact_pass.hip): reads with a fragment whose SEG regions did not fit
-  // a SegRec are classified again behind the retry pass, with region lists of any length.  Counters: [5] listed reads,
-  // [6] fragments of its queue, [7] its work counter, [20] pairs handed out of its pool
-  const bool exact_pass = n > 0 && p.seg && c->exact_pass;
   ExactPassLaunch xp{};
-  if (exact_pass) {
-    const uint64_t max_frag = protein ? max_read_len / 3 : max_read_len / 3 + 2;     // (max_read_len was tripled for protein reads)
-    size_redo_seg(xp, max_frag);
+  if (plan.exact_pass) {
+    if ((rc = bind_exact_seg(c, xp, plan.max_frag, kRedoFrags, b, s))) return rc;
     if ((rc = ensure(c->redo_bitmap, ((size_t)n / 32 + 2) * 4))) return rc;
     if ((rc = ensure(c->redo_list, (size_t)kRedoReads * 4))) return rc;
     if ((rc = ensure(c->redo_items, (size_t)kRedoFrags * sizeof(SegWork)))) return rc;
-    if ((rc = ensure(c->redo_index, (size_t)kRedoFrags * sizeof(uint2)))) return rc;
-    if ((rc = ensure(c->redo_pool, (size_t)kRedoPairs * 8))) return rc;
-    if ((rc = ensure(c->redo_work, (size_t)xp.seg_blocks * 16 * xp.cap_ints))) return rc;
-    if ((rc = ensure(c->redo_cls, (size_t)xp.seg_blocks * xp.cls_bytes))) return rc;
     KJ_HIP(hipMemsetAsync(c->redo_bitmap.p, 0, ((size_t)n / 32 + 2) * 4, s));
-    xp.ix = ix->dev; xp.d_ct = ix->d_ct; xp.st = ix->st; xp.p = p; xp.b = b; xp.sq = sq; xp.cnt = cnt;
+    xp.ix = ix->dev; xp.d_ct = ix->d_ct; xp.p = p; xp.sq = sq;
     xp.bitmap = static_cast<uint32_t *>(c->redo_bitmap.p); xp.list = static_cast<uint32_t *>(c->redo_list.p);
     xp.list_cap = kRedoReads;
-    xp.sq2 = SegQueue{static_cast<SegWork *>(c->redo_items.p), nullptr, cnt + 6, kRedoFrags};
-    xp.big = BigSeg{static_cast<uint2 *>(c->redo_index.p), static_cast<int32_t *>(c->redo_pool.p), cnt + 20, kRedoPairs};
-    xp.work = static_cast<int32_t *>(c->redo_work.p); xp.cls = static_cast<uint8_t *>(c->redo_cls.p);
-    xp.n_cu = c->n_cu; xp.stream = s;
+    xp.sq2 = SegQueue{static_cast<SegWork *>(c->redo_items.p), nullptr, cnt + kCntExactFrags, kRedoFrags};
+    xp.n_cu = c->n_cu;
   }
   VerboseOut vb{nullptr, nullptr, nullptr, nullptr, 0};
   if (c->verbose) {
     // columns 6/7: per read kVbAcc sequence numbers and room for 20 matched peptides
-    c->vb_text_cap = kaiju_gpu_verbose_text_stride((uint32_t)std::min<uint64_t>(max_pair, 0xffffffffull), 0) - 1;   // (max_pair: tripled for protein reads above)
+    c->vb_text_cap = kaiju_gpu_verbose_text_stride((uint32_t)std::min<uint64_t>(max_pair, 0xffffffffull), 0) - 1;   // (max_pair: tripled for protein reads)
     if ((rc = ensure(c->vb_nacc, (size_t)n * 4 + 16))) return rc;
     if ((rc = ensure(c->vb_acc, (size_t)n * kVbAcc * 4 + 16))) return rc;
     if ((rc = ensure(c->vb_tlen, (size_t)n * 4 + 16))) return rc;
@@ -2288,129 +2311,105 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
     KJ_HIP(hipMemsetAsync(c->vb_nacc.p, 0, (size_t)n * 4, s));
     KJ_HIP(hipMemsetAsync(c->vb_tlen.p, 0, (size_t)n * 4, s));
   }
+  const bool lane_wide = flow_lane_wide(plan.lane);
+  Params p_lane = p, p_second = p;
+  p_lane.flags |= plan.flags_lane; p_second.flags |= plan.flags_second;
   if (p.mode == 0) {
     const uint32_t si_cap = 16;
     if ((rc = ensure(c->scratch_main[0], lanes_main * si_cap * sizeof(SIEntry)))) return rc;
-    // every (fragment, end position) can yield at most one match
-    const uint32_t si_cap_retry = (uint32_t)std::min<uint64_t>(2 * max_pair + 64, 1u << 24);
-    int blocks_retry = c->blocks_retry;
-    while (blocks_retry > 1 && (uint64_t)blocks_retry * kBlock * si_cap_retry * sizeof(SIEntry) > (1ull << 30)) blocks_retry /= 2;
+    const uint32_t si_cap_retry = plan.si_cap_retry;
+    const int blocks_retry = plan.blocks_retry;
     if ((rc = ensure(c->scratch_retry[0], (uint64_t)blocks_retry * kBlock * si_cap_retry * sizeof(SIEntry)))) return rc;
-    if (n > 0) {
-      const bool xo = (p.flags & kParamXOrder) != 0;
+    if (plan.run) {
       SIEntry *si_main = static_cast<SIEntry *>(c->scratch_main[0].p);
       // the second-generation lane that serves this index (narrow: below 2^32 rows; wide: 64-bit positions)
-      auto launch_v2 = [&](const Params &pp, const WorkList &wl, bool counting, bool second = false) {
-        if (c->verbose) {
-          if (mem_narrow2) hipLaunchKernelGGL(k_mem_vb, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap, vb.acc);
-          else hipLaunchKernelGGL(k_mem_wide2_vb, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap, vb.acc);
-        } else
-        if (mem_narrow2) {
-          if (second && !xo) hipLaunchKernelGGL(k_mem_second, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
-          else if (counting) hipLaunchKernelGGL(k_mem_count, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
-          else if (xo) hipLaunchKernelGGL(k_mem_x, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
-          else hipLaunchKernelGGL(k_mem, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+      auto launch_v2 = [&](const Params &pp, const WorkList &wl, FlowInst inst, bool second) {
+        const dim3 grid(c->blocks_main);
+        if (inst == FlowInst::Verbose) {
+          if (!lane_wide) hipLaunchKernelGGL(k_mem_vb, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap, vb.acc);
+          else hipLaunchKernelGGL(k_mem_wide2_vb, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap, vb.acc);
+        } else if (!lane_wide) {
+          if (second) hipLaunchKernelGGL(k_mem_second, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          else if (inst == FlowInst::Counting) hipLaunchKernelGGL(k_mem_count, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          else if (inst == FlowInst::XOrder) hipLaunchKernelGGL(k_mem_x, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          else hipLaunchKernelGGL(k_mem, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
         } else {
-          if (counting) hipLaunchKernelGGL(k_mem_wide2_count, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
-          else if (xo) hipLaunchKernelGGL(k_mem_wide2_x, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
-          else hipLaunchKernelGGL(k_mem_wide2, dim3(c->blocks_main), blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          if (inst == FlowInst::Counting) hipLaunchKernelGGL(k_mem_wide2_count, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          else if (inst == FlowInst::XOrder) hipLaunchKernelGGL(k_mem_wide2_x, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
+          else hipLaunchKernelGGL(k_mem_wide2, grid, blk, 0, s, ix->dev, pp, b, wl, si_main, si_cap);
         }
       };
-      // the second-generation lanes leave the longest matches of every read in its hit record; k_mem_locate* behind the
-      // searches turn them into ids (round 1-4: reads with three and more matches, and kaijux, were walked by the search lane)
-      const bool defer = mem_v2;
-      Params pd = p;
-      if (defer) pd.flags |= kParamDeferLocate;
-      if (mem_v2) {
-        Params pm = pd;
-        if (lazy) pm.flags |= kParamLazySeg;
-        launch_v2(pm, wl_main, c->count_ops);
-      } else if (!ix->dev.mb_base)
-        hipLaunchKernelGGL(k_mem_v1, dim3(c->blocks_main), blk, 0, s, ix->dev, p, b, wl_main, si_main, si_cap, vb);
-      else
-        hipLaunchKernelGGL(k_mem_wide, dim3(c->blocks_main), blk, 0, s, ix->dev, p, b, wl_main, si_main, si_cap, vb);
+      switch (plan.lane) {
+        case FlowLane::MemV1: hipLaunchKernelGGL(k_mem_v1, dim3(c->blocks_main), blk, 0, s, ix->dev, p, b, wl_main, si_main, si_cap, vb); break;
+        case FlowLane::MemWideV1: hipLaunchKernelGGL(k_mem_wide, dim3(c->blocks_main), blk, 0, s, ix->dev, p, b, wl_main, si_main, si_cap, vb); break;
+        case FlowLane::Mem2: case FlowLane::MemWide2: launch_v2(p_lane, wl_main, plan.inst, false); break;
+        default: break;              // (the Greedy lanes: not in this mode)
+      }
       KJ_HIP(hipGetLastError());
       KJ_HIP(hipEventRecord(c->ev[3], s));
       uint32_t *todo = nullptr;
       const DevTaxonomy dt = tax ? tax->dev : DevTaxonomy{};
       CompactHit *const cmp = reinterpret_cast<CompactHit *>(d_compact);
-      if (fused) {
+      if (plan.fused) {
         if ((rc = ensure(c->seglist, (size_t)n * 4 + 16))) return rc;
         if ((rc = ensure(c->todo_list, (size_t)n * 4 + 16))) return rc;
         todo = static_cast<uint32_t *>(c->todo_list.p);
         uint32_t *seglist = static_cast<uint32_t *>(c->seglist.p);
-        if (tax) hipLaunchKernelGGL(k_mem_post1<true>, grid_reads, dim3(256), 0, s, ix->d_s1, ix->dev, p, b, dt, cmp, lazy ? 1 : 0, seglist, cnt + 22, todo, cnt + 26);
-        else hipLaunchKernelGGL(k_mem_post1<false>, grid_reads, dim3(256), 0, s, ix->d_s1, ix->dev, p, b, dt, cmp, lazy ? 1 : 0, seglist, cnt + 22, todo, cnt + 26);
+        hipLaunchKernelGGL(pick_mem_post1(tax != nullptr), grid_reads, dim3(256), 0, s, ix->d_s1, ix->dev, p, b, dt, cmp, lazy ? 1 : 0,
+                           seglist, cnt + kCntLazyList, todo, cnt + kCntTodoList);
         KJ_HIP(hipGetLastError());
       }
       if (lazy) {
         // reads whose longest matches lie in fragments that SEG would cut: listed, SEG pass for their fragments, the
-        // lists rewritten, searched again (counters: [22] listed reads, [23] work counter of that search)
+        // lists rewritten, searched again
         if ((rc = ensure(c->seglist, (size_t)n * 4 + 16))) return rc;
         uint32_t *seglist = static_cast<uint32_t *>(c->seglist.p);
-        if (!fused) hipLaunchKernelGGL(k_trigcheck, grid_reads, dim3(256), 0, s, ix->d_s1, p, b, seglist, cnt + 22);
-        hipLaunchKernelGGL(k_segflag, dim3(c->n_cu * 4), dim3(256), 0, s, p, ix->st, b, sq, seglist, cnt + 22, cnt + 3);
+        if (plan.trigcheck) hipLaunchKernelGGL(k_trigcheck, grid_reads, dim3(256), 0, s, ix->d_s1, p, b, seglist, cnt + kCntLazyList);
+        hipLaunchKernelGGL(k_segflag, dim3(c->n_cu * 4), dim3(256), 0, s, p, ix->st, b, sq, seglist, cnt + kCntLazyList, cnt + kCntErrFlags);
         launch_seg(c, s, p, ix->st, b, sq);
-        hipLaunchKernelGGL(k_seg_apply_list, dim3(c->n_cu * 4), blk, 0, s, ix->d_ct, p, b, sq, seglist, cnt + 22, cnt + 3);
+        hipLaunchKernelGGL(k_seg_apply_list, dim3(c->n_cu * 4), blk, 0, s, ix->d_ct, p, b, sq, seglist, cnt + kCntLazyList, cnt + kCntErrFlags);
         WorkList wl_seg;
-        wl_seg.counter = cnt + 23; wl_seg.reads = seglist; wl_seg.n_items_ptr = cnt + 22; wl_seg.n_items = 0;
+        wl_seg.counter = cnt + kCntLazyWork; wl_seg.reads = seglist; wl_seg.n_items_ptr = cnt + kCntLazyList; wl_seg.n_items = 0;
         wl_seg.retry_list = wl_main.retry_list; wl_seg.retry_count = wl_main.retry_count;
-        launch_v2(pd, wl_seg, false, true);
+        launch_v2(p_second, wl_seg, plan.inst_second, plan.mem_second);
         KJ_HIP(hipGetLastError());
       }
       hipLaunchKernelGGL(k_mem_retry, dim3(blocks_retry), blk, 0, s, ix->dev, p, b, wl_retry,
                          static_cast<SIEntry *>(c->scratch_retry[0].p), si_cap_retry, vb);
       KJ_HIP(hipGetLastError());
-      if (defer && c->verbose) {
+      if (plan.mem_verbose) {
         // columns 6 / 7 of the reads whose matches wait in their records (the retry pass above wrote its reads' own)
-        if (mem_narrow2) hipLaunchKernelGGL(k_mem_verbose<false>, grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
-        else hipLaunchKernelGGL(k_mem_verbose<true>, grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
+        hipLaunchKernelGGL(pick_mem_verbose(lane_wide), grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
         KJ_HIP(hipGetLastError());
       }
-      if (defer && !fused) {
-        if (mem_narrow2 && ix->dev.row_tax) {
-          hipLaunchKernelGGL(k_mem_locate<false>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 24);
-          hipLaunchKernelGGL(k_mem_locate_list<false>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 24);
-        }
-        else if (mem_narrow2) hipLaunchKernelGGL(k_mem_locate_team, grid_team, dim3(256), 0, s, ix->dev, p, b);
-        else if (ix->dev.row_tax) {
-          hipLaunchKernelGGL(k_mem_locate<true>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 24);
-          hipLaunchKernelGGL(k_mem_locate_list<true>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 24);
-        }
-        else hipLaunchKernelGGL(k_mem_locate_wide, grid_team, dim3(256), 0, s, ix->dev, p, b);
-        KJ_HIP(hipGetLastError());
-      }
-      if (exact_pass) {
+      launch_locate(c, s, plan.locate, p, b, loc_list, cnt + kCntLocListMem);
+      KJ_HIP(hipGetLastError());
+      if (plan.exact_pass) {
         xp.si = static_cast<SIEntry *>(c->scratch_retry[0].p); xp.si_cap = si_cap_retry; xp.blocks_search = blocks_retry;
         xp.vb = vb;
         KJ_HIP(kj_launch_exact_pass(xp));
       }
-      if (fused) {
+      if (plan.fused) {
         // the reads that were not through after k_mem_post1 (second search, retry pass, exact pass, matches of many rows)
-        if (tax) hipLaunchKernelGGL(k_mem_post2<true>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, dt, cmp, todo, cnt + 26);
-        else hipLaunchKernelGGL(k_mem_post2<false>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, dt, cmp, todo, cnt + 26);
+        hipLaunchKernelGGL(pick_mem_post2(tax != nullptr), dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, dt, cmp, todo, cnt + kCntTodoList);
         KJ_HIP(hipGetLastError());
       }
     } else KJ_HIP(hipEventRecord(c->ev[3], s));
   } else {
-    const uint32_t frag_max = max_read_len / 3 + 4;
+    const uint32_t frag_max = plan.max_read_len / 3 + 4;
     GreedyArrays ga;
     // (-v: 512 slots.  With 192, 54 of 250 000 benchmark reads ran out of slots and went to the retry pass - whose few lanes
     //  then worked 180 ms on them, next to 100 ms for everything else: profiles/r06_l41/g1_probe.txt.  82 bytes a slot:
     //  11 GB of scratch for a -v run in Greedy mode instead of 4)
     ga.pool_cap = (c->verbose && !c->g1_pool_set) ? std::max<uint32_t>(c->g1_pool, 512u) : c->g1_pool; ga.match_cap = c->g1_match;
-    // (-v: the VERBOSE instantiation of the second-generation lane unless KAIJU_GPU_VERBOSE_LANE=v1 - fragment positions must fit
-    //  the 16 bits of a GBestV's substitution positions, as in the lane itself)
-    const bool vb_g2 = c->verbose && !c->verbose_v1 && max_read_len / 3 + 4 < 65536;
-    const bool use_g2 = c->greedy2 && (!c->verbose || vb_g2);
-    const bool use_g3 = use_g2 && c->greedy3 && !c->verbose;
+    const bool lane2 = plan.lane != FlowLane::GreedyV1;       // greedy_lane2 (or the row-pool lane) runs the main pass
     // (the row-pool lane: one block per CU, kG3Pool rows each - its scratch in device memory is per ROW)
 #ifdef KJ_GREEDY3
-    const uint64_t lanes_g2 = use_g3 ? (uint64_t)c->n_cu * kG3Pool : lanes_main;
+    const uint64_t lanes_g2 = plan.lane == FlowLane::Greedy3 ? (uint64_t)c->n_cu * kG3Pool : lanes_main;
 #else
     const uint64_t lanes_g2 = lanes_main;
 #endif
-    if (!use_g2) {
+    if (!lane2) {
       if ((rc = ensure(c->scratch_main[0], lanes_main * ga.pool_cap * sizeof(GItem)))) return rc;
       if ((rc = ensure(c->scratch_main[1], lanes_main * ga.pool_cap * sizeof(uint16_t)))) return rc;
       if ((rc = ensure(c->scratch_main[2], lanes_main * ga.match_cap * sizeof(GMatch)))) return rc;
@@ -2440,17 +2439,16 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
       gr.bestv = static_cast<GBestV *>(c->vb_bestv_retry.p);
     }
     GreedyArrays2 g2{};
-    if (use_g2) {
+    if (lane2) {
       if ((rc = ensure(c->scratch_main[5], (lanes_g2 * (8 * kGSlotsAll) + 4) * sizeof(u128)))) return rc;
       if ((rc = ensure(c->scratch_main[6], (lanes_g2 * (kGSlotsAll - kGSlots) + 16) * sizeof(uint32_t)))) return rc;   // (+ slack: read 16 bytes at a time)
       if ((rc = ensure(c->scratch_main[7], lanes_g2 * kGMaxMAll * sizeof(GMatch2)))) return rc;
       if ((rc = ensure(c->scratch_main[8], lanes_g2 * (kGMaxMAll - kGMaxM) * sizeof(uint16_t)))) return rc;
-      const bool g_wide = ix->dev.mb_base != nullptr;
-      if ((rc = ensure(c->scratch_main[9], lanes_g2 * 64 * (g_wide ? sizeof(GBest2W) : sizeof(GBest2))))) return rc;
+      if ((rc = ensure(c->scratch_main[9], lanes_g2 * 64 * (lane_wide ? sizeof(GBest2W) : sizeof(GBest2))))) return rc;
       g2.pool = static_cast<u128 *>(c->scratch_main[5].p); g2.prio_ext = static_cast<uint32_t *>(c->scratch_main[6].p);
       g2.matches = static_cast<GMatch2 *>(c->scratch_main[7].p); g2.mq_ext = static_cast<uint16_t *>(c->scratch_main[8].p);
-      g2.best = g_wide ? nullptr : static_cast<GBest2 *>(c->scratch_main[9].p);
-      g2.bestw = g_wide ? static_cast<GBest2W *>(c->scratch_main[9].p) : nullptr;
+      g2.best = lane_wide ? nullptr : static_cast<GBest2 *>(c->scratch_main[9].p);
+      g2.bestw = lane_wide ? static_cast<GBest2W *>(c->scratch_main[9].p) : nullptr;
       g2.gate = c->greedy_gate;
       g2.bestv = nullptr; g2.vb = vb;
       if (c->verbose) {
@@ -2459,55 +2457,45 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
       }
     }
     call_mark("launch_batch: Greedy scratch in place");
-    if (n > 0) {
-      Params pg = p;
-      if (use_g2) pg.flags |= kParamDeferLocate;       // (greedy_lane2 leaves every read's best matches to k_mem_locate*)
-      const bool g_wide = ix->dev.mb_base != nullptr;
+    if (plan.run) {
+      const dim3 grid(c->blocks_main);
+      const bool counting = plan.inst == FlowInst::Counting;
+      switch (plan.lane) {
+        case FlowLane::Greedy2Wide:
+          if (plan.inst == FlowInst::Verbose) hipLaunchKernelGGL(k_greedy2_wide_vb, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          else if (counting) hipLaunchKernelGGL(k_greedy2_wide_count, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          else hipLaunchKernelGGL(k_greedy2_wide, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          break;
 #ifdef KJ_GREEDY3
-      if (use_g3 && c->count_ops)
-        hipLaunchKernelGGL(k_greedy3_count, dim3(c->n_cu), dim3(c->g3_threads), 0, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2, c->g3_split);
-      else if (use_g3)
-        hipLaunchKernelGGL(k_greedy3, dim3(c->n_cu), dim3(c->g3_threads), 0, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2, c->g3_split);
-      else
+        case FlowLane::Greedy3:
+          if (counting) hipLaunchKernelGGL(k_greedy3_count, dim3(c->n_cu), dim3(c->g3_threads), 0, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2, c->g3_split);
+          else hipLaunchKernelGGL(k_greedy3, dim3(c->n_cu), dim3(c->g3_threads), 0, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2, c->g3_split);
+          break;
+#else
+        case FlowLane::Greedy3:      // (a library without the row-pool lane: greedy_lane2, whose scratch is what was sized above)
 #endif
-      if (use_g2 && c->verbose && g_wide)
-        hipLaunchKernelGGL(k_greedy2_wide_vb, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else if (use_g2 && c->verbose)
-        hipLaunchKernelGGL(k_greedy2_vb, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else if (use_g2 && c->count_ops && g_wide)
-        hipLaunchKernelGGL(k_greedy2_wide_count, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else if (use_g2 && g_wide)
-        hipLaunchKernelGGL(k_greedy2_wide, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else if (use_g2 && c->count_ops)
-        hipLaunchKernelGGL(k_greedy2_count, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else if (use_g2)
-        hipLaunchKernelGGL(k_greedy2, dim3(c->blocks_main), blk, kGreedy2Lds, s, ix->dev, ix->d_ct, pg, sq, b, wl_main, g2);
-      else
-        hipLaunchKernelGGL(k_greedy, dim3(c->blocks_main), blk, 0, s, ix->dev, ix->d_ct, p, sq, b, wl_main, ga, vb);
+        case FlowLane::Greedy2:
+          if (plan.inst == FlowInst::Verbose) hipLaunchKernelGGL(k_greedy2_vb, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          else if (counting) hipLaunchKernelGGL(k_greedy2_count, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          else hipLaunchKernelGGL(k_greedy2, grid, blk, kGreedy2Lds, s, ix->dev, ix->d_ct, p_lane, sq, b, wl_main, g2);
+          break;
+        case FlowLane::GreedyV1:
+          hipLaunchKernelGGL(k_greedy, grid, blk, 0, s, ix->dev, ix->d_ct, p, sq, b, wl_main, ga, vb);
+          break;
+        default: break;              // (the MEM lanes: not in this mode)
+      }
       KJ_HIP(hipGetLastError());
       KJ_HIP(hipEventRecord(c->ev[3], s));
       hipLaunchKernelGGL(k_greedy_retry, dim3(c->blocks_retry), blk, 0, s, ix->dev, ix->d_ct, p, sq, b, wl_retry, gr, vb);
       KJ_HIP(hipGetLastError());
-      if ((pg.flags & kParamDeferLocate) && c->verbose) {
+      if (plan.mem_verbose) {
         // column 6 of the reads whose best matches wait in their records (the retry pass above wrote its reads' own columns)
-        if (g_wide) hipLaunchKernelGGL((k_mem_verbose<true, false>), grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
-        else hipLaunchKernelGGL((k_mem_verbose<false, false>), grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
+        hipLaunchKernelGGL(pick_greedy_verbose(lane_wide), grid_reads, dim3(256), 0, s, ix->dev, p, b, vb);
         KJ_HIP(hipGetLastError());
       }
-      if (pg.flags & kParamDeferLocate) {
-        if (g_wide && ix->dev.row_tax) {
-          hipLaunchKernelGGL(k_mem_locate<true>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 25);
-          hipLaunchKernelGGL(k_mem_locate_list<true>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 25);
-        }
-        else if (g_wide) hipLaunchKernelGGL(k_mem_locate_wide, grid_team, dim3(256), 0, s, ix->dev, p, b);
-        else if (ix->dev.row_tax) {
-          hipLaunchKernelGGL(k_mem_locate<false>, grid_reads, dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 25);
-          hipLaunchKernelGGL(k_mem_locate_list<false>, dim3(c->n_cu * 8), dim3(256), 0, s, ix->dev, p, b, loc_list, cnt + 25);
-        }
-        else hipLaunchKernelGGL(k_mem_locate_team, grid_team, dim3(256), 0, s, ix->dev, p, b);
-        KJ_HIP(hipGetLastError());
-      }
-      if (exact_pass) {
+      launch_locate(c, s, plan.locate, p, b, loc_list, cnt + kCntLocListGreedy);
+      KJ_HIP(hipGetLastError());
+      if (plan.exact_pass) {
         xp.g_pool = gr.pool; xp.g_ord = gr.ord; xp.g_matches = gr.matches; xp.g_best = gr.best; xp.g_bestv = gr.bestv;
         xp.g_pool_cap = gr.pool_cap; xp.g_match_cap = gr.match_cap; xp.blocks_search = c->blocks_retry;
         xp.vb = vb;
@@ -2515,7 +2503,7 @@ static int launch_batch(kaiju_gpu_ctx *c, const void *d_seqs, uint64_t seq_bytes
       }
     } else KJ_HIP(hipEventRecord(c->ev[3], s));
   }
-  if (tax && !fused && n > 0) {
+  if (plan.lca) {
     hipLaunchKernelGGL(k_lca, dim3((n + 255) / 256), dim3(256), 0, s, tax->dev, reinterpret_cast<const Hit *>(d_out), n,
                        reinterpret_cast<CompactHit *>(d_compact));
     KJ_HIP(hipGetLastError());
@@ -3056,8 +3044,8 @@ extern "C" int kaiju_gpu_get_op_counts(kaiju_gpu_ctx *ctx, uint64_t *out, uint32
   KJ_HIP(hipSetDevice(ctx->ix->device));
   KJ_HIP(hipDeviceSynchronize());
   unsigned long long v[kOpcN];
-  static_assert(kOpcOffsetBytes + sizeof v <= 1024, "the totals fit the counter block");
-  KJ_HIP(hipMemcpy(v, static_cast<const uint8_t *>(ctx->counters.p) + kOpcOffsetBytes, sizeof v, hipMemcpyDeviceToHost));
+  static_assert(kCntOpTotals * 4 + sizeof v <= kCntProf * 4, "the totals fit the counter block");
+  KJ_HIP(hipMemcpy(v, static_cast<const uint32_t *>(ctx->counters.p) + kCntOpTotals, sizeof v, hipMemcpyDeviceToHost));
   for (uint32_t x = 0; x < n_out && x < (uint32_t)kOpcN; x++) out[x] = v[x];
   return KAIJU_GPU_OK;
 }
@@ -3086,57 +3074,37 @@ extern "C" int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const
   for (uint64_t r = 0; r < n; r++) {
     if (off[2 * r + 1] < off[2 * r] || off[2 * r + 2] != off[2 * r + 1]) return fail(KAIJU_GPU_ERR_ARG, "offsets must be non-decreasing, mates empty");
     const uint64_t l = off[2 * r + 1] - off[2 * r];
-    if (l > 0x10000000ull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "protein read longer than 2^28");
     if (l > max_len) max_len = l;
   }
   if (seq_bytes && !seqs) return fail(KAIJU_GPU_ERR_ARG, "seqs is NULL");
-  // the buffers of launch_batch, sized as there
-  const uint64_t pep_bytes = 2 * seq_bytes + kPepPerRead * n + 32 + 256;
-  const uint64_t n_frag_slots = 2 * ((2 * seq_bytes) / (p.m + 1) + 7ull * n) + 8;
-  if (n_frag_slots >= 0xffffffffull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "batch too large: split it (fragment slots exceed 2^32)");
-  const uint64_t seg_cap = std::min<uint64_t>(n_frag_slots / 2 + 8, 0x00ffffffull);
+  // the buffers of launch_batch, sized and bound as there: the plan of this context for a batch of these reads
+  // (with its refusals: a read over 2^28, fragment slots over 2^32)
+  const FlowPlan plan = plan_call(c, seq_bytes, n, 0, (uint32_t)std::min<uint64_t>(max_len, 0xffffffffull), false);
   int rc;
+  if ((rc = plan_status(plan))) return rc;
   if ((rc = ensure(c->h_seqs, seq_bytes + 64))) return rc;
   if ((rc = ensure(c->h_off, (2 * (size_t)n + 1) * 8))) return rc;
   if ((rc = ensure(c->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
-  if ((rc = ensure(c->pep, pep_bytes))) return rc;
-  if ((rc = ensure(c->frags, n_frag_slots * sizeof(Frag)))) return rc;
-  if ((rc = ensure(c->meta, (size_t)n * sizeof(ReadMeta) + 16))) return rc;
-  if ((rc = ensure(c->counters, 4096))) return rc;
-  if ((rc = ensure(c->seg_items, seg_cap * sizeof(SegWork)))) return rc;
-  if ((rc = ensure(c->seg_recs, seg_cap * sizeof(SegRec)))) return rc;
-  ExactPassLaunch xp{};
-  if (exact) {
-    size_redo_seg(xp, max_len);
-    if ((rc = ensure(c->redo_index, (size_t)std::max<uint64_t>(seg_cap, kRedoFrags) * sizeof(uint2)))) return rc;
-    if ((rc = ensure(c->redo_pool, (size_t)kRedoPairs * 8))) return rc;
-    if ((rc = ensure(c->redo_work, (size_t)xp.seg_blocks * 16 * xp.cap_ints))) return rc;
-    if ((rc = ensure(c->redo_cls, (size_t)xp.seg_blocks * xp.cls_bytes))) return rc;
-  }
   hipStream_t s = c->stream;
+  Batch b;
+  SegQueue sq;
+  if ((rc = bind_batch(c, plan, c->h_seqs.p, static_cast<const uint64_t *>(c->h_off.p), n, 0, c->h_hits.p, b, sq))) return rc;
+  ExactPassLaunch xp{};
+  // (every fragment of stage 1's queue gets an entry of the pool's index here)
+  if (exact && (rc = bind_exact_seg(c, xp, plan.max_frag, std::max<uint64_t>(plan.seg_cap, kRedoFrags), b, s))) return rc;
   if (seq_bytes) KJ_HIP(hipMemcpyAsync(c->h_seqs.p, seqs, seq_bytes, hipMemcpyHostToDevice, s));
   KJ_HIP(hipMemcpyAsync(c->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  Batch b;
-  b.seqs = static_cast<const uint8_t *>(c->h_seqs.p); b.off = static_cast<const uint64_t *>(c->h_off.p); b.n_reads = n; b.paired = 0;
-  b.pep = static_cast<uint8_t *>(c->pep.p); b.frags = static_cast<Frag *>(c->frags.p);
-  b.meta = static_cast<ReadMeta *>(c->meta.p); b.hits = static_cast<Hit *>(c->h_hits.p);
   uint32_t *cnt = static_cast<uint32_t *>(c->counters.p);
-  SegQueue sq;
-  sq.items = static_cast<SegWork *>(c->seg_items.p); sq.recs = static_cast<SegRec *>(c->seg_recs.p);
-  sq.count = cnt + 4; sq.cap = (uint32_t)seg_cap;
-  KJ_HIP(hipMemsetAsync(cnt, 0, 1024, s));
+  KJ_HIP(hipMemsetAsync(cnt, 0, kCntProf * sizeof(uint32_t), s));
   KJ_HIP(hipEventRecord(c->ev[0], s));
-  hipLaunchKernelGGL(k_fragments_protein, dim3((n + kFragBlock - 1) / kFragBlock), dim3(kFragBlock), 0, s, ix->d_ct, p, ix->st, b, sq, cnt + 3);
+  launch_stage1(c, s, plan, p, b, sq, cnt + kCntErrFlags);
   KJ_HIP(hipGetLastError());
   KJ_HIP(hipEventRecord(c->ev[1], s));
   if (!exact) {
     launch_seg(c, s, p, ix->st, b, sq);
     KJ_HIP(hipGetLastError());
   } else {
-    xp.st = ix->st; xp.b = b; xp.cnt = cnt; xp.stream = s;
     xp.sq2 = SegQueue{sq.items, nullptr, sq.count, sq.cap};               // stage 1's queue is the exact pass's here
-    xp.big = BigSeg{static_cast<uint2 *>(c->redo_index.p), static_cast<int32_t *>(c->redo_pool.p), cnt + 20, kRedoPairs};
-    xp.work = static_cast<int32_t *>(c->redo_work.p); xp.cls = static_cast<uint8_t *>(c->redo_cls.p);
     KJ_HIP(kj_launch_redo_seg(xp));
   }
   for (int e = 2; e <= 4; e++) KJ_HIP(hipEventRecord(c->ev[e], s));
@@ -3144,9 +3112,9 @@ extern "C" int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const
   c->last_n = n;
   KJ_HIP(hipStreamSynchronize(s));
   // the fragment lists, the queue and what the SEG kernels wrote
-  uint32_t hc[24];
+  uint32_t hc[kCntExactPairs + 1];
   KJ_HIP(hipMemcpy(hc, cnt, sizeof hc, hipMemcpyDeviceToHost));
-  const uint32_t queued = std::min<uint32_t>(hc[4], sq.cap);
+  const uint32_t queued = std::min<uint32_t>(hc[kCntSegQueue], sq.cap);
   const uint64_t used_slots = frag_base(off, n, p.m);                     // (slots of the reads in front of a read behind the last)
   std::vector<ReadMeta> hm(n);
   KJ_HIP(hipMemcpy(hm.data(), c->meta.p, (size_t)n * sizeof(ReadMeta), hipMemcpyDeviceToHost));
@@ -3161,7 +3129,7 @@ extern "C" int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const
   } else {
     hidx.resize(queued);
     if (queued) KJ_HIP(hipMemcpy(hidx.data(), xp.big.index, (size_t)queued * sizeof(uint2), hipMemcpyDeviceToHost));
-    hpool.resize(2 * (size_t)std::min<uint32_t>(hc[20], kRedoPairs));
+    hpool.resize(2 * (size_t)std::min<uint32_t>(hc[kCntExactPairs], kRedoPairs));
     if (!hpool.empty()) KJ_HIP(hipMemcpy(hpool.data(), xp.big.lr, hpool.size() * 4, hipMemcpyDeviceToHost));
   }
   uint64_t nf = 0, nl = 0;
@@ -3220,11 +3188,11 @@ extern "C" int kaiju_gpu_get_stats(kaiju_gpu_ctx *ctx, kaiju_gpu_stats *stats) {
   KJ_HIP(hipEventElapsedTime(&t12, ctx->ev[1], ctx->ev[2]));
   KJ_HIP(hipEventElapsedTime(&t23, ctx->ev[2], ctx->ev[3]));
   KJ_HIP(hipEventElapsedTime(&t34, ctx->ev[3], ctx->ev[4]));
-  uint32_t cnt[8] = {0};
+  uint32_t cnt[kCntSegQueue + 1] = {0};
   KJ_HIP(hipMemcpy(cnt, ctx->counters.p, sizeof cnt, hipMemcpyDeviceToHost));
   if (getenv("KAIJU_GPU_PRINT_STATS")) {
     unsigned long long acc[6] = {0};
-    KJ_HIP(hipMemcpy(acc, static_cast<uint32_t *>(ctx->counters.p) + 8, sizeof acc, hipMemcpyDeviceToHost));
+    KJ_HIP(hipMemcpy(acc, static_cast<uint32_t *>(ctx->counters.p) + kCntLaneStats, sizeof acc, hipMemcpyDeviceToHost));
     if (ctx->params.mode == 0)
       fprintf(stderr, "[kj stats] lane-iters %llu step %llu kmer %llu lf %llu | sum over waves of max iters %llu, max passes %llu\n",
               acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]);
@@ -3238,7 +3206,7 @@ extern "C" int kaiju_gpu_get_stats(kaiju_gpu_ctx *ctx, kaiju_gpu_stats *stats) {
     static const char *names[PM_N] = {"HEAD", "LOAD", "LOADFILL", "STEP", "KMER", "LF1", "SA", "META", "FRAG", "FILL", "TAIL", "END_MATCH",
                                       "START_J", "NEXT_FRAG", "LOC_INIT", "LOC_NEXT_SI", "LOC_ROW", "FINISH"};
     unsigned long long pv[3 * PM_N];
-    KJ_HIP(hipMemcpy(pv, static_cast<uint8_t *>(ctx->counters.p) + 1024, sizeof pv, hipMemcpyDeviceToHost));
+    KJ_HIP(hipMemcpy(pv, static_cast<uint32_t *>(ctx->counters.p) + kCntProf, sizeof pv, hipMemcpyDeviceToHost));
     unsigned long long tot = 0;
     for (int x = 0; x < PM_N; x++) tot += pv[3 * x];
     fprintf(stderr, "[kj prof] section        cycles%%   entries/read  lanes/entry   cycles/entry   (k_mem main launch; n_reads %u, total wave-cycles %llu)\n", ctx->last_n, tot);
@@ -3252,7 +3220,7 @@ extern "C" int kaiju_gpu_get_stats(kaiju_gpu_ctx *ctx, kaiju_gpu_stats *stats) {
                                       "HANDOUT", "LOAD", "LOAD10", "STEP", "KMER", "LF1", "SA", "VM_RANK", "VM_PUSH", "META", "FRAG",
                                       "FILL", "MLOAD", "END_MATCH", "START_J", "LOC_ROW", "TAIL"};
     unsigned long long pv[3 * PS_N];
-    KJ_HIP(hipMemcpy(pv, static_cast<uint8_t *>(ctx->counters.p) + 1024, sizeof pv, hipMemcpyDeviceToHost));
+    KJ_HIP(hipMemcpy(pv, static_cast<uint32_t *>(ctx->counters.p) + kCntProf, sizeof pv, hipMemcpyDeviceToHost));
     unsigned long long tot = 0;
     for (int x = 0; x < PS_N; x++) tot += pv[3 * x];
     fprintf(stderr, "[kj prof] section        cycles%%   entries/read  lanes/entry   cycles/entry   (n_reads %u, total wave-cycles %llu)\n", ctx->last_n, tot);
@@ -3265,16 +3233,16 @@ extern "C" int kaiju_gpu_get_stats(kaiju_gpu_ctx *ctx, kaiju_gpu_stats *stats) {
   stats->n_reads = ctx->last_n;
   if (getenv("KAIJU_GPU_OVF_STATS") && ctx->params.mode == 1) {
     uint32_t why[8] = {0};
-    KJ_HIP(hipMemcpy(why, static_cast<uint32_t *>(ctx->counters.p) + 40, sizeof why, hipMemcpyDeviceToHost));
+    KJ_HIP(hipMemcpy(why, static_cast<uint32_t *>(ctx->counters.p) + kCntOvfWhy, sizeof why, hipMemcpyDeviceToHost));
     fprintf(stderr, "[kaiju_gpu] Greedy reads sent to the retry pass, by reason: key/sequence bits %u, queue full %u, original too long %u, "
                     "SEG piece too long %u, variant too long %u, matches per fragment %u, wide interval %u\n",
             why[0], why[1], why[2], why[3], why[4], why[5], why[6]);
   }
-  stats->n_overflow_retries = cnt[2];
-  stats->n_seg_fragments = cnt[4];
+  stats->n_overflow_retries = cnt[kCntRetryLen];
+  stats->n_seg_fragments = cnt[kCntSegQueue];
   // bit 0 (a SegRec overflowed in the MEM split of the main pass) is settled by the exact pass, which reports its own
   // failures: 4 = region pool exhausted, 8 = more reads than its list holds
-  stats->error_flags = (ctx->kp.seg && ctx->exact_pass) ? (cnt[3] & ~1u) : cnt[3];
+  stats->error_flags = (ctx->kp.seg && ctx->exact_pass) ? (cnt[kCntErrFlags] & ~1u) : cnt[kCntErrFlags];
   stats->ms_translate = t01;
   stats->ms_seg = t12;
   stats->ms_search = t23;

@@ -8,6 +8,29 @@
 
 #include "kj_core.h"
 
+// The counter buffer of a batch (4096 bytes, zeroed in front of every call up to kCntProf): its uint32 slots
+enum CounterSlot : uint32_t {
+  kCntMainWork = 0,        // work counter of the main search
+  kCntRetryWork = 1,       // ... of the retry pass
+  kCntRetryLen = 2,        // length of the retry list
+  kCntErrFlags = 3,        // error flags: 1 a SegRec overflowed (settled by the exact pass), 2 SEG queue full, 4 region pool of
+                           // the exact pass exhausted, 8 more reads than its list holds
+  kCntSegQueue = 4,        // fragments in the SEG queue
+  kCntExactReads = 5,      // the exact pass: listed reads,
+  kCntExactFrags = 6,      // ... fragments of its queue,
+  kCntExactWork = 7,       // ... its work counter,
+  kCntLaneStats = 8,       // base of six uint64 of the lanes' loop statistics (KAIJU_GPU_PRINT_STATS)
+  kCntExactPairs = 20,     // ... (left, right) pairs handed out of its pool
+  kCntLazyList = 22,       // lazy SEG: listed reads,
+  kCntLazyWork = 23,       // ... work counter of their second search
+  kCntLocListMem = 24,     // reads whose matches hold many rows (k_mem_locate_list): MEM,
+  kCntLocListGreedy = 25,  // ... Greedy
+  kCntTodoList = 26,       // reads k_mem_post1 left to k_mem_post2
+  kCntOvfWhy = 40,         // base of eight counts: Greedy reads sent to the retry pass, by reason (KAIJU_GPU_OVF_STATS)
+  kCntOpTotals = kj::kOpcOffsetBytes / 4,   // base of the totals of the counting lanes (kOpcN uint64)
+  kCntProf = 256           // base of the section profiles of -DKJ_PROF builds (byte 1024 .. 4096)
+};
+
 struct ExactPassLaunch {
   kj::DevIndex ix;
   const kj::ConstTables *d_ct;
@@ -15,8 +38,7 @@ struct ExactPassLaunch {
   kj::Params p;
   kj::Batch b;
   kj::SegQueue sq;            // queue and records of the main SEG pass
-  uint32_t *cnt;              // counters of the batch: [3] error flags, [5] listed reads, [6] queue of the exact pass,
-                              // [7] its work counter, [20] pairs handed out of the pool
+  uint32_t *cnt;              // counters of the batch (CounterSlot)
   uint32_t *bitmap, *list;    // one bit per read (zeroed); the listed reads
   uint32_t list_cap;
   kj::SegQueue sq2;           // queue of the exact pass (recs unused)

@@ -144,24 +144,24 @@ k_redo_greedy(DevIndex ix, const ConstTables *__restrict__ g_ct, Params p, SegQu
 // step (3) alone: SEG with lists of any length over the queue a.sq2
 hipError_t kj_launch_redo_seg(const ExactPassLaunch &a) {
   hipLaunchKernelGGL(k_redo_seg, dim3(a.seg_blocks), dim3(kXSegBlock), 0, a.stream, a.st, a.b, a.sq2, a.big, a.work, a.cls, a.cap_ints,
-                     a.cls_bytes, a.cnt + 3);
+                     a.cls_bytes, a.cnt + kCntErrFlags);
   return hipGetLastError();
 }
 
 hipError_t kj_launch_exact_pass(const ExactPassLaunch &a) {
   hipStream_t s = a.stream;
   uint32_t *cnt = a.cnt;
-  hipLaunchKernelGGL(k_redo_collect, dim3(a.n_cu), dim3(256), 0, s, a.sq, a.bitmap, a.list, cnt + 5, a.list_cap, cnt + 3);
+  hipLaunchKernelGGL(k_redo_collect, dim3(a.n_cu), dim3(256), 0, s, a.sq, a.bitmap, a.list, cnt + kCntExactReads, a.list_cap, cnt + kCntErrFlags);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_redo_fragments, dim3(64), dim3(kXFragBlock), 0, s, a.d_ct, a.p, a.st, a.b, a.sq2, cnt + 3, a.list, cnt + 5);
+  hipLaunchKernelGGL(k_redo_fragments, dim3(64), dim3(kXFragBlock), 0, s, a.d_ct, a.p, a.st, a.b, a.sq2, cnt + kCntErrFlags, a.list, cnt + kCntExactReads);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = kj_launch_redo_seg(a)) != hipSuccess) return e;
   WorkList wl;
-  wl.counter = cnt + 7; wl.reads = a.list; wl.n_items_ptr = cnt + 5; wl.n_items = 0;
+  wl.counter = cnt + kCntExactWork; wl.reads = a.list; wl.n_items_ptr = cnt + kCntExactReads; wl.n_items = 0;
   wl.retry_list = nullptr; wl.retry_count = nullptr;
   if (a.p.mode == 0) {
-    hipLaunchKernelGGL(k_redo_apply, dim3(64), dim3(kXFragBlock), 0, s, a.d_ct, a.p, a.b, a.big, a.list, cnt + 5);
+    hipLaunchKernelGGL(k_redo_apply, dim3(64), dim3(kXFragBlock), 0, s, a.d_ct, a.p, a.b, a.big, a.list, cnt + kCntExactReads);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_redo_mem, dim3(a.blocks_search), dim3(kXBlock), 0, s, a.ix, a.p, a.b, wl, a.si, a.si_cap, a.vb);
   } else {

@@ -18,6 +18,7 @@
 #include "../../kaiju_amd/csrc/host_index.h"
 #include "../../kaiju_amd/csrc/host_tables.h"
 #include "../../kaiju_amd/csrc/kj_core.h"
+#include "../../kaiju_amd/csrc/kj_flow.h"
 #include "../../kaiju_amd/csrc/kj_greedy3.h"
 #include "../../kaiju_amd/csrc/fmi_stream.h"
 
@@ -275,6 +276,30 @@ const char *emu_seq_name(void *h, uint32_t iseq) {
 }
 const char *emu_alphabet(void *h) { return ((EmuIndex *)h)->packed.alphabet.c_str(); }
 
+// The product's flow plan (kj_flow.h: plan_flow) as plain integers, for tests/test_flow_plan.py.
+//   ix[7]   blocks64, kline, kline_k, kmer64, kmer_k, wide, row_tax
+//   sw[17]  mode, m, seed_length, seg, Params::flags (kParamXOrder | kParamProtein), verbose, verbose_v1, mem_v1, stage1_old,
+//           stage1_lane, lazy_seg, fused_post, exact_pass, greedy2 (2 = what a context sets at creation: flow_greedy2), greedy3,
+//           count_ops, blocks_retry
+//   call[5] n, paired, max_read_len, seq_bytes, records16
+//   out[27] the fields of FlowPlan in the order of their declaration
+void emu_flow_plan(const uint64_t *ix, const uint64_t *sw, const uint64_t *call, uint64_t *out) {
+  const FlowIndex fi{ix[0] != 0, ix[1] != 0, (uint32_t)ix[2], ix[3] != 0, (uint32_t)ix[4], ix[5] != 0, ix[6] != 0};
+  FlowSwitches s;
+  s.p = Params{};
+  s.p.mode = (int32_t)sw[0]; s.p.m = (uint32_t)sw[1]; s.p.seed_length = (uint32_t)sw[2]; s.p.seg = (int32_t)sw[3]; s.p.flags = (uint32_t)sw[4];
+  s.verbose = sw[5] != 0; s.verbose_v1 = sw[6] != 0; s.mem_v1 = sw[7] != 0; s.stage1_old = sw[8] != 0; s.stage1_lane = sw[9] != 0;
+  s.lazy_seg = sw[10] != 0; s.fused_post = sw[11] != 0; s.exact_pass = sw[12] != 0;
+  s.greedy2 = sw[13] == 2 ? (s.p.mode == 1 && flow_greedy2(fi, s.p.seed_length)) : sw[13] != 0;
+  s.greedy3 = sw[14] != 0; s.count_ops = sw[15] != 0; s.blocks_retry = (int)sw[16];
+  const FlowPlan f = plan_flow(fi, s, FlowCall{(uint32_t)call[0], call[1] != 0, (uint32_t)call[2], call[3], call[4] != 0});
+  const uint64_t v[27] = {(uint64_t)f.status, f.run, (uint64_t)f.stage1, (uint64_t)f.seg, f.seg_apply, (uint64_t)f.lane, (uint64_t)f.inst,
+                          (uint64_t)f.inst_second, f.mem_second, f.flags_lane, f.flags_second, f.fused, f.trigcheck, f.mem_verbose,
+                          (uint64_t)f.locate, f.exact_pass, f.lca, f.clear_out, f.max_read_len, f.max_pair, f.pep_bytes, f.n_frag_slots,
+                          f.seg_cap, f.max_frag, f.si_cap_retry, f.per_lane, (uint64_t)f.blocks_retry};
+  for (int x = 0; x < 27; x++) out[x] = v[x];
+}
+
 // fragments of one batch (stage 1): returns per-read lists as ASCII for comparison
 // frag_dump receives, per read, a "#" line followed by one "key:PEPTIDE" line per fragment
 int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const uint64_t *off, uint32_t n,
@@ -286,9 +311,30 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   p.mode = gp->mode; p.m = gp->min_fragment_length; p.mismatches = gp->mismatches; p.min_score = gp->min_score;
   p.seed_length = gp->seed_length; p.seg = gp->seg; p.max_matches_SI = gp->max_matches_SI; p.max_match_ids = gp->max_match_ids;
   if (p.mismatches > (uint32_t)kMaxMismatch) return KAIJU_GPU_ERR_UNSUPPORTED;
-  // as kaiju_gpu_create does
   if (ix->xmode && p.mode == 0 && !getenv("KAIJU_EMU_NO_XORDER")) p.flags |= kParamXOrder;   // (switch: shows that a test sees the order)
-  if (gp->input_is_protein) { p.flags |= kParamProtein; if (paired) return KAIJU_GPU_ERR_ARG; }
+  if (gp->input_is_protein) p.flags |= kParamProtein;
+  uint32_t maxlen = 0;
+  for (uint32_t r = 0; r < n; r++) {
+    uint32_t l1 = (uint32_t)(off[2 * r + 1] - off[2 * r]), l2 = (uint32_t)(off[2 * r + 2] - off[2 * r + 1]);
+    if (l1 > maxlen) maxlen = l1;
+    if (l2 > maxlen) maxlen = l2;
+  }
+  // which flow: the product's plan (kj_flow.h) for this index, these parameters and this batch; the KAIJU_EMU_* variables are
+  // the switches of a context.  KAIJU_EMU_LANE (any value): the first-generation lanes, as KAIJU_GPU_MEM_LANE / _GREEDY_LANE=v1
+  const char *lane_env = getenv("KAIJU_EMU_LANE");
+  const FlowIndex fi = flow_index(d);
+  FlowSwitches sw;
+  sw.p = p;
+  sw.verbose = g_vb.n_acc != nullptr; sw.verbose_v1 = getenv("KAIJU_EMU_VERBOSE_V1") != nullptr;
+  sw.mem_v1 = lane_env != nullptr; sw.greedy2 = p.mode == 1 && flow_greedy2(fi, p.seed_length) && !lane_env;
+  sw.stage1_old = getenv("KAIJU_EMU_STAGE1_OLD") != nullptr; sw.lazy_seg = !getenv("KAIJU_EMU_LAZY_OFF");
+  sw.blocks_retry = p.mode == 0 ? 16 : 4;                   // (as kaiju_gpu_create; the one lane here has no use for them)
+  const FlowPlan plan = plan_flow(fi, sw, FlowCall{n, paired != 0, maxlen ? maxlen : 1, n ? off[2 * (uint64_t)n] : 0, false});
+  if (plan.status == FlowStatus::ProteinPaired) return KAIJU_GPU_ERR_ARG;
+  if (plan.status != FlowStatus::Ok) return KAIJU_GPU_ERR_UNSUPPORTED;
+  const bool lazy = plan.seg == FlowSeg::Lazy;
+  const bool lane_wide = flow_lane_wide(plan.lane);
+  const bool lane_vb = plan.inst == FlowInst::Verbose;       // (the VERBOSE instantiations of the second-generation lanes)
   Batch b;
   b.seqs = (const uint8_t *)seqs; b.off = off; b.n_reads = n; b.paired = paired;
   std::vector<uint8_t> pep((size_t)pep_base(off, n) + 512, 0);
@@ -297,14 +343,8 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   std::vector<Hit> hits(n);
   memset(hits.data(), 0, sizeof(Hit) * n);
   b.pep = pep.data(); b.frags = frags.data(); b.meta = meta.data(); b.hits = hits.data();
-  uint32_t maxlen = 0;
-  for (uint32_t r = 0; r < n; r++) {
-    uint32_t l1 = (uint32_t)(off[2 * r + 1] - off[2 * r]), l2 = (uint32_t)(off[2 * r + 2] - off[2 * r + 1]);
-    if (l1 > maxlen) maxlen = l1;
-    if (l2 > maxlen) maxlen = l2;
-  }
   uint32_t err = 0;
-  // stage 1 -> SEG pass -> (MEM) apply, exactly the kernel sequence of capi.hip
+  // stage 1 -> SEG pass -> (MEM) apply
   uint32_t seg_count = 0;
   const uint32_t seg_cap = (uint32_t)(frags.size() / 2 + 8);
   std::vector<SegWork> seg_items(seg_cap);
@@ -314,25 +354,14 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   // peptides are staged (here: linear scratch) and copied out, as the kernel does with its LDS area
   std::vector<uint8_t> stage((size_t)4 * maxlen + 256);
   const bool staged = !getenv("KAIJU_EMU_NOSTAGE");
-  // which flow (capi.hip: launch_batch): the fast stage 1 for mates up to kS1MaxLen nucleotides; MEM on the second-generation
-  // lanes then looks at SEG lazily
-  const char *lane_env = getenv("KAIJU_EMU_LANE");
-  // (verbose output: the VERBOSE instantiations of the second-generation lanes + mem_verbose_read, as capi.hip; KAIJU_EMU_VERBOSE_V1
-  //  = the first-generation lanes, which wrote columns 6 / 7 until round 6)
-  const bool vb_v2 = g_vb.n_acc && !getenv("KAIJU_EMU_VERBOSE_V1");
-  const bool mem_v2 = p.mode == 0 && d.blocks64 && (d.kmer32 || (d.mb_base && d.kmer64)) && !lane_env && (!g_vb.n_acc || vb_v2);
-  const bool fast1 = !(p.flags & kParamProtein) && !getenv("KAIJU_EMU_STAGE1_OLD") && maxlen <= kS1MaxLenLong && p.m >= 1 && p.m <= 64;
-  const bool long1 = maxlen > kS1MaxLen;
-  const bool lazy = fast1 && mem_v2 && p.seg && !getenv("KAIJU_EMU_LAZY_OFF");
-  const bool trig1 = fast1 && p.seg && !lazy;
   Stage1Tables s1tab;
   build_stage1_tables(ix->ct, ix->st, s1tab);
-  if (p.flags & kParamProtein) {
+  if (plan.stage1 == FlowStage1::Protein) {
     uint8_t code[256];
     memset(code, 0, sizeof code);
     for (uint32_t a = 0; a < 20; a++) protein_code_entry(ix->ct, a, code);
     for (uint32_t r = 0; r < n; r++) build_fragments_protein(ix->ct, code, p, TrigCtx{ix->st.ent_g32, ix->st.ent_locut32}, b, sq, r, &err);
-  } else if (fast1) {
+  } else if (plan.stage1 != FlowStage1::Old) {
     const Stage1Tables &s1 = s1tab;
     uint32_t codes[2 * kS1ListCap];
     alignas(4) uint8_t cnt[kS1CntStride];
@@ -342,14 +371,17 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       for (auto &x : codes) x = 0xdeadbeefu;
       memset(cnt, 0xee, sizeof cnt);
       memset(tsbuf, 0xee, sizeof tsbuf);
-      if (trig1 && long1) build_fragments_fast<true, kS1UnitsLong>(s1, p, b, sq, r, &err, ln);
-      else if (long1) build_fragments_fast<false, kS1UnitsLong>(s1, p, b, sq, r, &err, ln);
-      else if (trig1) build_fragments_fast<true>(s1, p, b, sq, r, &err, ln);
-      else build_fragments_fast<false>(s1, p, b, sq, r, &err, ln);
+      switch (plan.stage1) {
+        case FlowStage1::LongTrig: build_fragments_fast<true, kS1UnitsLong>(s1, p, b, sq, r, &err, ln); break;
+        case FlowStage1::Long: build_fragments_fast<false, kS1UnitsLong>(s1, p, b, sq, r, &err, ln); break;
+        case FlowStage1::FastTrig: build_fragments_fast<true>(s1, p, b, sq, r, &err, ln); break;
+        // (Team: k_fragments_team has the contract of build_fragments_fast<false>; tests/test_stage1_team.py covers its code)
+        default: build_fragments_fast<false>(s1, p, b, sq, r, &err, ln); break;
+      }
     }
   } else
   for (uint32_t r = 0; r < n; r++) build_fragments(ix->ct, p, TrigCtx{ix->st.ent_g32, ix->st.ent_locut32}, b, sq, r, &err, staged ? stage.data() : nullptr, 4, (uint32_t)(stage.size() / 4));
-  if (p.seg && !lazy) {
+  if (plan.seg == FlowSeg::Eager) {
     if (getenv("KAIJU_EMU_SEG_COUNT")) {                 // how much work the eager SEG pass gets (tools: sizing of k_seg)
       uint64_t tl = 0;
       for (uint32_t s = 0; s < seg_count && s < seg_cap; s++) tl += b.frags[b.meta[seg_items[s].read].frag + seg_items[s].frag].len;
@@ -360,7 +392,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
     std::vector<uint8_t> segcls(64);
     for (uint32_t s = 0; s < seg_count && s < seg_cap; s++)
       seg_compute(cx, emu_coop(), b, p, sq, s, segstage.data(), (uint32_t)segstage.size(), segwork, segcls.data(), [] {});
-    if (p.mode == 0) for (uint32_t r = 0; r < n; r++) seg_apply_mem(ix->ct, p, b, sq, r, &err);
+    if (plan.seg_apply) for (uint32_t r = 0; r < n; r++) seg_apply_mem(ix->ct, p, b, sq, r, &err);
   }
   if (frag_dump) {
     const char *alpha = ix->packed.alphabet.c_str();
@@ -409,26 +441,25 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
     }
     if (p.mode == 0) {
       LaneScratch ls{si.data(), (uint32_t)si.size(), win};
-      const char *v = getenv("KAIJU_EMU_LANE");        // "v1", "wide" or default (v2 where possible)
+      // (KAIJU_EMU_LANE=wide, emulation only: the first-generation lane with 64-bit positions on a narrow index too)
+      const bool force_wide = lane_env && !strcmp(lane_env, "wide");
       const bool xo = (p.flags & kParamXOrder) != 0;
-      if (vb_v2) ls.vbm = g_vb.acc;
+      if (lane_vb) ls.vbm = g_vb.acc;
       auto lane_v2 = [&](const Params &pp, const WorkList &w2) {
-        if (vb_v2) {                                     // (k_mem_vb / k_mem_wide2_vb)
-          if (d.kmer32) { if (xo) mem_lane2<false, true, false, true>(d, pp, b, w2, ls); else mem_lane2<false, false, false, true>(d, pp, b, w2, ls); }
+        if (lane_vb) {                                     // (k_mem_vb / k_mem_wide2_vb)
+          if (!lane_wide) { if (xo) mem_lane2<false, true, false, true>(d, pp, b, w2, ls); else mem_lane2<false, false, false, true>(d, pp, b, w2, ls); }
           else { if (xo) mem_lane2<true, true, false, true>(d, pp, b, w2, ls); else mem_lane2<true, false, false, true>(d, pp, b, w2, ls); }
         }
-        else if (d.kmer32) { if (xo) mem_lane2<false, true>(d, pp, b, w2, ls); else mem_lane2<false>(d, pp, b, w2, ls); }
+        else if (!lane_wide) { if (xo) mem_lane2<false, true>(d, pp, b, w2, ls); else mem_lane2<false>(d, pp, b, w2, ls); }
         else { if (xo) mem_lane2<true, true>(d, pp, b, w2, ls); else mem_lane2<true>(d, pp, b, w2, ls); }
       };
-      if (mem_v2 && pass == 0) {
-        // (capi.hip: the lanes leave the longest matches in the hit records, k_mem_locate* behind the searches walk them)
-        Params pd = p;
-        pd.flags |= kParamDeferLocate;
-        Params pm = pd;
-        if (lazy) pm.flags |= kParamLazySeg;
+      if ((plan.lane == FlowLane::Mem2 || plan.lane == FlowLane::MemWide2) && pass == 0) {
+        // (the lanes leave the longest matches in the hit records, the locate behind the searches walks them)
+        Params pd = p, pm = p;
+        pd.flags |= plan.flags_second; pm.flags |= plan.flags_lane;
         lane_v2(pm, wl);
         if (lazy) {
-          // k_trigcheck, k_segflag, k_seg, k_seg_apply_list and the search of the listed reads (capi.hip)
+          // k_trigcheck (or its part of k_mem_post1), k_segflag, k_seg, k_seg_apply_list and the search of the listed reads
           std::vector<uint32_t> seglist;
           for (uint32_t r = 0; r < n; r++) {
             const uint32_t vv = hits[r].reserved;
@@ -478,17 +509,16 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
           if (getenv("KAIJU_EMU_PRINT_LAZY")) fprintf(stderr, "[emu] lazy SEG: %u of %u reads listed\n", nlist, n);
         }
       }
-      else if (!d.mb_base && !(v && !strcmp(v, "wide")) && pass == 0) mem_lane<uint32_t>(d, p, b, wl, ls, g_vb);
+      else if (plan.lane == FlowLane::MemV1 && !force_wide && pass == 0) mem_lane<uint32_t>(d, p, b, wl, ls, g_vb);
       else mem_lane<uint64_t>(d, p, b, wl, ls, g_vb);
     } else {
       GreedyScratch gs;
       gs.pool = pool.data(); gs.pool_cap = (uint32_t)pool.size(); gs.ord = ord.data();
       gs.matches = matches.data(); gs.match_cap = (uint32_t)matches.size();
       gs.best = bestv.data(); gs.win = win;
-      const char *v = getenv("KAIJU_EMU_LANE");        // "v1" or default (v2 where possible)
       std::vector<GBestV> bestvv(64);
       gs.bestv = g_vb.n_acc ? bestvv.data() : nullptr;
-      if (d.blocks64 && (d.kline || (d.mb_base && d.kmer64)) && !v && pass == 0 && (!g_vb.n_acc || vb_v2)) {
+      if (plan.lane != FlowLane::GreedyV1 && pass == 0) {
         alignas(16) uint32_t lds_win[kGWinStride], lds_mq[kGMqStride], lds_prio[kGPrioStride];
         for (auto &x : lds_win) x = 0xdeadbeefu;
         for (auto &x : lds_mq) x = 0xdeadbeefu;
@@ -506,13 +536,15 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
         for (auto &x : lds_sub) x = 0xdeadbeefu;
         g2.sub = lds_sub;
         Params pg = p;
-        pg.flags |= kParamDeferLocate;
-        const char *g3e = getenv("KAIJU_EMU_GREEDY");       // "3": the row-pool lane (kj_greedy3.h; narrow indexes) - the product's KAIJU_GPU_GREEDY_LANE=v3
+        pg.flags |= plan.flags_lane;
+        // (KAIJU_EMU_GREEDY=3, applied after the plan: the row-pool lane (kj_greedy3.h; narrow indexes), which the product runs only in
+        //  -DKJ_GREEDY3 builds with KAIJU_GPU_GREEDY_LANE=v3)
+        const char *g3e = getenv("KAIJU_EMU_GREEDY");
         std::vector<GBestV> bestv2(64);
-        if (vb_v2) { g2.bestv = bestv2.data(); g2.vb = g_vb; g2.lane = 0; }      // (k_greedy2_vb / k_greedy2_wide_vb)
-        if (vb_v2 && d.mb_base) greedy_lane2<false, true, true>(d, ix->ct, pg, sq, b, wl, g2);
-        else if (vb_v2) greedy_lane2<false, false, true>(d, ix->ct, pg, sq, b, wl, g2);
-        else if (d.mb_base) greedy_lane2<false, true>(d, ix->ct, pg, sq, b, wl, g2);
+        if (lane_vb) { g2.bestv = bestv2.data(); g2.vb = g_vb; g2.lane = 0; }      // (k_greedy2_vb / k_greedy2_wide_vb)
+        if (lane_vb && lane_wide) greedy_lane2<false, true, true>(d, ix->ct, pg, sq, b, wl, g2);
+        else if (lane_vb) greedy_lane2<false, false, true>(d, ix->ct, pg, sq, b, wl, g2);
+        else if (lane_wide) greedy_lane2<false, true>(d, ix->ct, pg, sq, b, wl, g2);
         else if (!(g3e && !strcmp(g3e, "3"))) greedy_lane2(d, ix->ct, pg, sq, b, wl, g2);
         else {
           // third generation (kj_greedy3.h): the read's state in a row of "LDS"; here a pool of one row
@@ -532,24 +564,30 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       } else greedy_lane(d, ix->ct, p, sq, b, wl, gs, g_vb);
     }
   }
-  // k_mem_verbose (capi.hip): columns 6 / 7 of the reads whose matches wait in their records, in front of the locate
-  if (mem_v2 && vb_v2) for (uint32_t r = 0; r < n; r++) { if (d.mb_base) mem_verbose_read<true>(d, p, b, r, g_vb); else mem_verbose_read<false>(d, p, b, r, g_vb); }
+  // k_mem_verbose: columns 6 / 7 of the reads whose matches wait in their records, in front of the locate
   // (Greedy: the VERBOSE lane wrote column 7 itself; column 6 from its records)
-  if (p.mode != 0 && vb_v2) for (uint32_t r = 0; r < n; r++) { if (d.mb_base) mem_verbose_read<true, false>(d, p, b, r, g_vb); else mem_verbose_read<false, false>(d, p, b, r, g_vb); }
-  // k_mem_locate (capi.hip): behind the main, the second and the retry search
-  const bool locate_pass = true;
-  // (indexes without the row -> sequence table are located by teams of lanes on the device: k_mem_locate_wide / _team; here a
-  //  team of four whose walks run one after the other, KAIJU_EMU_LOCATE_SERIAL=1: the one-lane function)
-  if (locate_pass) for (uint32_t r = 0; r < n; r++) {
-    const bool serial = getenv("KAIJU_EMU_LOCATE_SERIAL") != nullptr;
-    if (d.mb_base && d.row_tax && !serial) { if (!mem_locate_read<true>(d, p, &hits[r], 8)) mem_locate_read<true, true>(d, p, &hits[r]); }   // (k_mem_locate<true>, k_mem_locate_list<true>)
-    else if (d.mb_base) { if (serial) mem_locate_read<true>(d, p, &hits[r]); else { TeamSerial<4> tm; mem_locate_read_team<true, 4>(d, p, &hits[r], tm); } }
-    else if (serial) mem_locate_read<false>(d, p, &hits[r]);
-    else if (d.row_tax) { if (!mem_locate_read<false>(d, p, &hits[r], 8)) mem_locate_read<false, true>(d, p, &hits[r]); }   // (k_mem_locate, k_mem_locate_list)
-    else { TeamSerial<4> tm; mem_locate_read_team<false, 4>(d, p, &hits[r], tm); }
+  if (plan.mem_verbose) for (uint32_t r = 0; r < n; r++) {
+    if (p.mode == 0) { if (lane_wide) mem_verbose_read<true>(d, p, b, r, g_vb); else mem_verbose_read<false>(d, p, b, r, g_vb); }
+    else { if (lane_wide) mem_verbose_read<true, false>(d, p, b, r, g_vb); else mem_verbose_read<false, false>(d, p, b, r, g_vb); }
   }
-  // the exact pass (kj_core.h: BigSeg), as capi.hip's k_redo_* kernels run it behind the retry pass
-  if (p.seg && n > 0) {
+  // the locate behind the main, the second and the retry search.  A fused post-search (k_mem_post1 / _post2) is not emulated:
+  // its reads get the per-read locate by the row -> taxon table, which it holds.  The walks by teams of lanes (k_mem_locate_team /
+  // _wide) are a team of four here whose walks run one after the other
+  FlowLocate locate = plan.locate == FlowLocate::Fused ? FlowLocate::RowTax : plan.locate;
+  // (KAIJU_EMU_LOCATE_SERIAL=1, emulation only, applied after the plan: the one-lane walk in place of whatever the plan names)
+  const bool serial = getenv("KAIJU_EMU_LOCATE_SERIAL") != nullptr && locate != FlowLocate::InLane;
+  for (uint32_t r = 0; r < n; r++) {
+    if (serial) { if (lane_wide) mem_locate_read<true>(d, p, &hits[r]); else mem_locate_read<false>(d, p, &hits[r]); continue; }
+    switch (locate) {
+      case FlowLocate::RowTaxWide: if (!mem_locate_read<true>(d, p, &hits[r], 8)) mem_locate_read<true, true>(d, p, &hits[r]); break;   // (k_mem_locate<true>, k_mem_locate_list<true>)
+      case FlowLocate::RowTax: if (!mem_locate_read<false>(d, p, &hits[r], 8)) mem_locate_read<false, true>(d, p, &hits[r]); break;   // (k_mem_locate, k_mem_locate_list)
+      case FlowLocate::WideWalk: { TeamSerial<4> tm; mem_locate_read_team<true, 4>(d, p, &hits[r], tm); break; }
+      case FlowLocate::Team: { TeamSerial<4> tm; mem_locate_read_team<false, 4>(d, p, &hits[r], tm); break; }
+      default: break;                                        // (InLane: the first-generation lanes walked themselves)
+    }
+  }
+  // the exact pass (kj_core.h: BigSeg), as the k_redo_* kernels run it behind the retry pass
+  if (plan.exact_pass) {
     std::vector<uint32_t> redo;
     std::vector<char> seen(n, 0);
     for (uint32_t s2 = 0; s2 < seg_count && s2 < seg_cap; s2++) {
@@ -577,7 +615,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
         if (protein) build_fragments_protein(ix->ct, code, p, TrigCtx{ix->st.ent_g32, ix->st.ent_locut32}, b, sq2, r, &err);
         else build_fragments(ix->ct, p, TrigCtx{ix->st.ent_g32, ix->st.ent_locut32}, b, sq2, r, &err, nullptr, 4, 0);
       }
-      const uint32_t max_frag = protein ? maxlen : maxlen / 3 + 2;
+      const uint32_t max_frag = (uint32_t)plan.max_frag;
       const int cap_ints = (int)(2 * max_frag + 4);
       std::vector<int32_t> work2((size_t)4 * cap_ints);
       std::vector<uint8_t> cls2((size_t)max_frag + 64);
