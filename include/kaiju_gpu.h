@@ -462,6 +462,61 @@ int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy
                                     char *out_text, uint64_t out_cap, kaiju_gpu_parse_info *info_parse,
                                     kaiju_gpu_format_info *info_format);
 
+/* ---- the lines of kaiju -v on the device: hits and matches in, text out ------------------------------------ */
+/* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi WITH -v, as HIP passes
+   (kaiju_amd/csrc/format_verbose.hip; the rules: kj_format_verbose.h): the decision of the three-column lines, and for a
+   classified read "C\t<name>\t<taxon>\t<best>\t<ids>\t<accs>\t<peptides>\n" - the ids of the hit in ascending order, the sorted
+   set of the accessions (names of the matched database sequences up to their last '_'), the peptides as k_vb_pack packs them.
+   The accession strings come from a table of the index that is uploaded on request: */
+/* Host only, no GPU: per sequence name the length of its prefix up to, not including, the last '_' and the rank of that prefix
+   among the sorted distinct prefixes of all nseq names (std::string order; equal prefixes share a rank; 0xffffffff and length
+   0: the name has no '_'). */
+int kaiju_accession_ranks(const char *const *names, uint32_t nseq, uint32_t *rank, uint32_t *prefix_len);
+/* The accession table of the index to its device: the prefixes as one blob, per sequence offset (8 bytes), length and rank (4
+   each).  Explicit - a run without -v never pays for it - and idempotent; concurrent callers are serialised.  An index
+   loaded with KAIJU_GPU_IDS_SEQUENCE: KAIJU_GPU_ERR_UNSUPPORTED. */
+int kaiju_gpu_index_upload_accessions(kaiju_gpu_index *ix);
+/* bytes of the table in HBM, 0 before the upload */
+uint64_t kaiju_gpu_index_accession_bytes(const kaiju_gpu_index *ix);
+typedef struct kaiju_gpu_format_verbose_info {
+  uint64_t text_bytes;             /* size of the whole text, whether or not it fitted                                      */
+  uint32_t n_records, n_classified;/* records formatted (= n), 'C' lines among them                                         */
+  uint32_t overflow;               /* 1: text_bytes > out_cap; the whole lines that fit are written, no byte at or behind   */
+                                   /* out_cap is touched                                                                    */
+  uint32_t n_inexact;              /* records whose compact info carries KAIJU_HIT_INEXACT                                  */
+  uint32_t n_truncated;            /* classified records whose peptides were cut (text_len > text_cap)                      */
+  uint32_t reserved;
+} kaiju_gpu_format_verbose_info;   /* 32 bytes */
+/* All pointers are device pointers on the context's GPU.  d_hits: n hit records; d_recs: the n compact records k_lca makes of
+   them; d_off: 2n + 1; d_n_acc: n; d_acc_iseq: n x KAIJU_GPU_MAX_ACC; d_text_pos (n) / d_text_len (n): where the peptides of
+   record r lie in d_pep and how many there are (more than text_cap: cut there, counted in n_truncated); d_names_text:
+   names_bytes (below 2^32 - 32) bytes the spans d_names (n) point into.  d_out must be 16-byte aligned (KAIJU_GPU_ERR_ARG
+   otherwise).  Asynchronous on `stream` (NULL: the context's own); nothing waits for the host.  Without an uploaded accession
+   table: KAIJU_GPU_ERR_ARG.  The scratch lives in the context and grows when a call needs more: 24 bytes per record and a
+   shadow of the output of out_cap bytes (so out_cap is a capacity to choose with care, not a safe huge number). */
+int kaiju_gpu_format_verbose_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *d_hits, const kaiju_gpu_compact *d_recs,
+                                    const uint64_t *d_off, uint32_t n, int paired, const uint32_t *d_n_acc,
+                                    const uint32_t *d_acc_iseq, const uint64_t *d_text_pos, const uint32_t *d_text_len,
+                                    const void *d_pep, uint32_t text_cap, const void *d_names_text, uint64_t names_bytes,
+                                    const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
+                                    kaiju_gpu_format_verbose_info *d_info, void *stream);
+/* The same with host pointers: what kaiju_gpu_classify_batch_verbose_packed returns (hits, vout, text_pos, text, text_bytes),
+   the compact records and the names.  vout[r].text_len above text_cap is cut at text_cap; a record is counted as truncated
+   when that happens or when vout[r].truncated is set.  Everything goes up, *info and the bytes written come down; blocks.
+   out[0 .. out_cap): only the bytes of the lines written change. */
+int kaiju_gpu_format_verbose(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hits, const kaiju_gpu_verbose *vout, const uint64_t *text_pos,
+                             const char *text, uint64_t text_bytes, uint32_t text_cap, const kaiju_gpu_compact *recs,
+                             const uint64_t *off, uint32_t n, int paired, const char *names_text, uint64_t names_bytes,
+                             const kaiju_gpu_name_span *names, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info);
+/* Reads in, the text of kaiju -v out: the verbose classification of kaiju_gpu_classify_batch_verbose_packed, k_vb_pack, the LCA
+   on the device and the passes above on the context's stream.  The one synchronisation inside is the read-back of the text's
+   size in front of the write pass (the library owns and sizes the output).  *text (text_bytes bytes) stays valid until the next
+   verbose call on this context.  No hit record, accession array or peptide string crosses to the host. */
+int kaiju_gpu_classify_batch_verbose_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *seqs, const uint64_t *off,
+                                          uint32_t n_reads, int paired, const char *names_text, uint64_t names_bytes,
+                                          const kaiju_gpu_name_span *names, const char **text, uint64_t *text_bytes,
+                                          kaiju_gpu_format_verbose_info *info);
+
 /* ---- several processes of a node, one per GPU: the gather --------------- */
 /* BASELINE north star: "reads shard embarrassingly across the GPUs of one node with the index replicated per GPU and per-GPU
    hit lists gathered with a single RCCL gather over xGMI".  The reference has no exchange (its threads append to one output

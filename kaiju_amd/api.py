@@ -80,6 +80,11 @@ assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
 
+FORMAT_VERBOSE_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"), ("n_classified", "<u4"), ("overflow", "<u4"),
+                                      ("n_inexact", "<u4"), ("n_truncated", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_format_verbose_info
+assert FORMAT_VERBOSE_INFO_DTYPE.itemsize == 32
+
+
 class KaijuGpuError(RuntimeError):
     pass
 
@@ -148,6 +153,19 @@ def lib():
     L.kaiju_gpu_format_evalue_table.argtypes = [C.c_void_p, C.c_uint32]
     L.kaiju_gpu_classify_text_to_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
                                                   C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    if hasattr(L, "kaiju_accession_ranks"):      # (a library linked from a source list of its own may lack accessions.cpp)
+        L.kaiju_accession_ranks.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "kaiju_gpu_index_upload_accessions"):       # (an older build loaded through KAIJU_GPU_LIB for an A/B run has none)
+        L.kaiju_gpu_index_upload_accessions.argtypes = [C.c_void_p]
+        L.kaiju_gpu_index_accession_bytes.restype = C.c_uint64
+        L.kaiju_gpu_index_accession_bytes.argtypes = [C.c_void_p]
+        L.kaiju_gpu_format_verbose_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                      C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_format_verbose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_classify_batch_verbose_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
+                                                            C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -225,6 +243,12 @@ class Index:
         out = np.empty(n_bytes, dtype=np.uint8)
         _check(L.kaiju_gpu_index_read_array(self._h, which, offset, n_bytes, out.ctypes.data))
         return out
+
+    def upload_accessions(self) -> int:
+        """kaiju_gpu_index_upload_accessions: the accession table of column 6 of kaiju -v to the device (explicit, idempotent);
+        returns its bytes in HBM"""
+        _check(lib().kaiju_gpu_index_upload_accessions(self._h))
+        return int(lib().kaiju_gpu_index_accession_bytes(self._h))
 
     def close(self):
         if self._h:
@@ -550,6 +574,59 @@ class Classifier:
                                                      len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
                                                      out.ctypes.data, ocap, info.ctypes.data, finfo.ctypes.data))
         return {"text": out[: int(finfo[0]["text_bytes"])].tobytes(), "info": info[0], "format_info": finfo[0]}
+
+    def format_verbose(self, hits: np.ndarray, v: np.ndarray, text_pos: np.ndarray, text, recs: np.ndarray, off: np.ndarray, names_text,
+                       names: np.ndarray, paired=False, text_cap=0xffffffff, out_cap=None, out=None):
+        """what classify_verbose_packed returns (hit records, kaiju_gpu_verbose records, positions, the packed peptides), the
+        compact records, off[], the text the names lie in and the name spans to the lines of kaiju -v
+        (kaiju_gpu_format_verbose): host buffers, blocking.  Returns (out, info): out is a uint8 array of which the lines
+        written have changed (out_cap bytes), info a FORMAT_VERBOSE_INFO_DTYPE record.  Index.upload_accessions() first."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        v = np.ascontiguousarray(v, dtype=VERBOSE_DTYPE)
+        text_pos = np.ascontiguousarray(text_pos, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=COMPACT_DTYPE)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        pep = np.frombuffer(bytes(text) + b"\0", dtype=np.uint8)
+        nt = np.frombuffer(bytes(names_text) + b"\0", dtype=np.uint8)
+        n = len(recs)
+        assert len(off) == 2 * n + 1 and len(names) == n and len(hits) == n and len(v) == n and len(text_pos) == n
+        assert out_cap is not None or out is not None
+        cap = int(out_cap) if out_cap is not None else len(out)
+        if out is None:
+            out = np.zeros(cap + 1, dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) >= cap
+        info = np.zeros(1, dtype=FORMAT_VERBOSE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_format_verbose(self._h, hits.ctypes.data, v.ctypes.data, text_pos.ctypes.data, pep.ctypes.data, len(pep) - 1, int(text_cap),
+                                              recs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, nt.ctypes.data, len(nt) - 1, names.ctypes.data,
+                                              out.ctypes.data, cap, info.ctypes.data))
+        return out, info[0]
+
+    def format_verbose_device(self, d_hits_ptr: int, d_recs_ptr: int, d_off_ptr: int, n: int, d_n_acc_ptr: int, d_acc_iseq_ptr: int,
+                              d_text_pos_ptr: int, d_text_len_ptr: int, d_pep_ptr: int, text_cap: int, d_names_text_ptr: int, names_bytes: int,
+                              d_names_ptr: int, d_out_ptr: int, out_cap: int, d_info_ptr: int, paired=False, stream: int = 0):
+        """the same for device-resident buffers (raw pointers; d_out 16-byte aligned): kaiju_gpu_format_verbose_device,
+        asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_format_verbose_device(self._h, d_hits_ptr or None, d_recs_ptr or None, d_off_ptr or None, n, 1 if paired else 0,
+                                                     d_n_acc_ptr or None, d_acc_iseq_ptr or None, d_text_pos_ptr or None, d_text_len_ptr or None,
+                                                     d_pep_ptr or None, int(text_cap), d_names_text_ptr or None, names_bytes, d_names_ptr or None,
+                                                     d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def classify_verbose_text(self, dtax: "DeviceTaxonomy", seqs: np.ndarray, off: np.ndarray, names_text, names: np.ndarray, paired=False):
+        """reads in, the lines of kaiju -v out (kaiju_gpu_classify_batch_verbose_text).  Returns (text as bytes - a copy, the
+        library's own is valid until the context's next verbose call -, a FORMAT_VERBOSE_INFO_DTYPE record)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        nt = np.frombuffer(bytes(names_text) + b"\0", dtype=np.uint8)
+        n = (len(off) - 1) // 2
+        assert len(names) == n
+        text = C.c_void_p()
+        nbytes = C.c_uint64()
+        info = np.zeros(1, dtype=FORMAT_VERBOSE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_classify_batch_verbose_text(self._h, dtax._h, seqs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, nt.ctypes.data,
+                                                           len(nt) - 1, names.ctypes.data, C.byref(text), C.byref(nbytes), info.ctypes.data))
+        return (C.string_at(text.value, nbytes.value) if nbytes.value else b""), info[0]
 
     OP_COUNT_NAMES = ("kmer_lookups", "update_si", "update_si_lines", "lf_steps", "lf_lines", "sa_samples", "read_meta",
                       "frag_desc", "window_fills", "term_searches", "si_spills", "hits", "multi_letter_steps", "items_read",

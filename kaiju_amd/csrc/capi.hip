@@ -43,6 +43,7 @@
 #include "exact_pass.h"
 #include "kj_ingest.h"
 #include "kj_format.h"
+#include "kj_format_verbose.h"
 // Libraries linked from a source list of their own (the compile-time variants of tests/tools/mem_variants.sh: search lanes
 // only) need not hold ingest.hip: the two functions are weak references here, and without them the entry points below say
 // KAIJU_GPU_ERR_UNSUPPORTED.  kaiju_amd/build.py always links ingest.hip.
@@ -52,6 +53,13 @@ __attribute__((weak)) decltype(kj_ingest_free) kj_ingest_free;
 __attribute__((weak)) decltype(kj_format_launch) kj_format_launch;
 __attribute__((weak)) decltype(kj_format_written) kj_format_written;
 __attribute__((weak)) decltype(kj_format_free) kj_format_free;
+// (format_verbose.hip and accessions.cpp likewise)
+__attribute__((weak)) decltype(kj_fv_lengths) kj_fv_lengths;
+__attribute__((weak)) decltype(kj_fv_total) kj_fv_total;
+__attribute__((weak)) decltype(kj_fv_write) kj_fv_write;
+__attribute__((weak)) decltype(kj_fv_written) kj_fv_written;
+__attribute__((weak)) decltype(kj_fv_free) kj_fv_free;
+extern "C" __attribute__((weak)) decltype(kaiju_accession_ranks) kaiju_accession_ranks;
 #ifdef KJ_GREEDY3                    // the experimental row-pool Greedy lane: variant builds only
 #include "kj_greedy3.h"
 #endif
@@ -1053,6 +1061,12 @@ struct kaiju_gpu_index {
   uint64_t tpos_bytes = 0;        // bytes of DevIndex::sa_tpos5 (fp.sa_full also counts the row -> taxon table of a wide index)
   std::vector<std::string> names;
   int id_mode = 0;                // KAIJU_GPU_IDS_TAXON / KAIJU_GPU_IDS_SEQUENCE
+  // the accession table (kaiju_gpu_index_upload_accessions; the pointers are in `allocs`), read and written under g_acc_mutex
+  const uint8_t *acc_blob = nullptr;
+  const uint64_t *acc_off = nullptr;
+  const uint32_t *acc_len = nullptr, *acc_rank = nullptr;
+  uint64_t acc_bytes = 0;
+  bool acc_ready = false;
   ~kaiju_gpu_index() {
     (void)hipSetDevice(device);
     for (void *p : allocs) (void)hipFree(p);
@@ -1966,6 +1980,8 @@ struct kaiju_gpu_ctx {
   kj_format_scratch *format = nullptr;                 // the output lines (format.hip): line lengths and offsets, decisions
   DevBuf fmt_pw, fmt_out, fmt_info;                    // ... the table of its E-value gate, the staging of its host-pointer entry points
   bool fmt_pw_ok = false;                              // (kjf::build_pow_table's verdict)
+  kj_fv_scratch *format_v = nullptr;                   // the lines of -v (format_verbose.hip): lengths, offsets, the shadow
+  DevBuf fv_out, fv_info, fv_trunc, fv_total;          // ... and the staging of its host-pointer entry points
   kaiju_gpu_stats stats{};
   uint32_t last_n = 0;
   uint32_t max_read_len = 1024;
@@ -1974,7 +1990,8 @@ struct kaiju_gpu_ctx {
     (void)hipSetDevice(ix->device);
     if (ingest) kj_ingest_free(ingest);
     if (format && kj_format_free) kj_format_free(format);
-    DevBuf *all[] = {&fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
+    if (format_v && kj_fv_free) kj_fv_free(format_v);
+    DevBuf *all[] = {&fv_out, &fv_info, &fv_trunc, &fv_total, &fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
                      &vb_nacc, &vb_acc, &vb_tlen, &vb_text, &vb_bestv, &vb_bestv_retry, &vb_packed, &vb_pos,
                      &redo_bitmap, &redo_list, &redo_items, &redo_index, &redo_pool, &redo_work, &redo_cls};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
@@ -2662,10 +2679,9 @@ extern "C" int kaiju_gpu_lca_batch_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_ta
   return KAIJU_GPU_OK;
 }
 
-// (the part both entry points share: classification, k_vb_pack, the records / accessions / packed text fetched - the text
-//  into ctx->vb_host, read r's at pos[r])
-static int verbose_core(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int paired, kaiju_gpu_hit *out,
-                        kaiju_gpu_verbose *vout, std::vector<uint64_t> &pos, std::vector<uint32_t> &tlen) {
+// (the device half: classification and k_vb_pack queued on the context's stream; records in ctx->h_hits, accessions in
+//  vb_nacc / vb_acc, lengths in vb_tlen, the packed text in vb_packed with read r's at vb_pos[r], vb_pos[n_reads] = its size)
+static int verbose_queue(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int paired) {
   ctx->verbose = true;
   int rc = classify_host_buffers(ctx, seqs, off, n_reads, paired);
   ctx->verbose = false;
@@ -2686,6 +2702,15 @@ static int verbose_core(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *of
   hipLaunchKernelGGL(k_vb_pack, dim3((n_reads + 255) / 256), dim3(256), 0, s, vbd, n_reads, al, static_cast<uint8_t *>(ctx->vb_packed.p),
                      static_cast<uint64_t *>(ctx->vb_pos.p), d_total);
   KJ_HIP(hipGetLastError());
+  return KAIJU_GPU_OK;
+}
+// (the part both entry points share: classification, k_vb_pack, the records / accessions / packed text fetched - the text
+//  into ctx->vb_host, read r's at pos[r])
+static int verbose_core(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int paired, kaiju_gpu_hit *out,
+                        kaiju_gpu_verbose *vout, std::vector<uint64_t> &pos, std::vector<uint32_t> &tlen) {
+  int rc = verbose_queue(ctx, seqs, off, n_reads, paired);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
   std::vector<uint32_t> &nacc = ctx->vb_h_nacc, &acc = ctx->vb_h_acc;
   if (nacc.size() < n_reads) nacc.resize(n_reads);
   if (acc.size() < (size_t)n_reads * kVbAcc) acc.resize((size_t)n_reads * kVbAcc);
@@ -3004,6 +3029,242 @@ extern "C" int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_g
   if (rc) return rc;
   if ((rc = format_download(ctx, s, out_text, out_cap, info_format))) return rc;
   if (info_format->overflow) return fail(KAIJU_GPU_ERR_ARG, "the output text needs more than out_cap bytes");
+  return KAIJU_GPU_OK;
+  });
+}
+
+// ---- the lines of kaiju -v on the device (format_verbose.hip) -----------------------------------------------------
+static std::mutex g_acc_mutex;      // the accession tables of all indexes: upload against upload, upload against the readers below
+static int no_format_verbose() {
+  if (!kj_fv_lengths || !kaiju_accession_ranks) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "this library was linked without format_verbose.hip / accessions.cpp");
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_index_upload_accessions(kaiju_gpu_index *ix) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_verbose()) return rc;
+  if (!ix) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "an index of sequence ids (kaijux / kaijup) has no accession column");
+  std::lock_guard<std::mutex> lk(g_acc_mutex);
+  if (ix->acc_ready) return KAIJU_GPU_OK;
+  const size_t nseq = ix->names.size();
+  if (nseq >= 0xffffffffull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "more than 2^32 - 2 sequences");
+  std::vector<const char *> ptr(nseq);
+  for (size_t i = 0; i < nseq; i++) ptr[i] = ix->names[i].c_str();
+  std::vector<uint32_t> rank(nseq + 1), len(nseq + 1);
+  if (int rc = kaiju_accession_ranks(ptr.data(), (uint32_t)nseq, rank.data(), len.data())) return fail(rc, "kaiju_accession_ranks");
+  std::vector<uint64_t> aoff(nseq + 1);
+  uint64_t total = 0;
+  for (size_t i = 0; i < nseq; i++) {
+    if (len[i] > kjv::kMaxPrefix) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a sequence name of the index is longer than 2^24 bytes");
+    aoff[i] = total; total += len[i];
+  }
+  aoff[nseq] = total;
+  std::vector<uint8_t> blob((size_t)total + 1);
+  for (size_t i = 0; i < nseq; i++) if (len[i]) memcpy(blob.data() + aoff[i], ptr[i], len[i]);
+  KJ_HIP(hipSetDevice(ix->device));
+  void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  const void *src[4] = {blob.data(), aoff.data(), len.data(), rank.data()};
+  const size_t bytes[4] = {(size_t)total + 1, (nseq + 1) * 8, (nseq + 1) * 4, (nseq + 1) * 4};
+  for (int k = 0; k < 4; k++) {
+    if (hipMalloc(&d[k], bytes[k] + 16) != hipSuccess || hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      for (int j = 0; j <= k; j++) if (d[j]) (void)hipFree(d[j]);
+      return fail(KAIJU_GPU_ERR_NOMEM, "the accession table could not be uploaded");
+    }
+  }
+  for (int k = 0; k < 4; k++) ix->allocs.push_back(d[k]);
+  ix->acc_blob = static_cast<const uint8_t *>(d[0]); ix->acc_off = static_cast<const uint64_t *>(d[1]);
+  ix->acc_len = static_cast<const uint32_t *>(d[2]); ix->acc_rank = static_cast<const uint32_t *>(d[3]);
+  ix->acc_bytes = total + 16 * (uint64_t)nseq;
+  ix->acc_ready = true;
+  return KAIJU_GPU_OK;
+  });
+}
+extern "C" uint64_t kaiju_gpu_index_accession_bytes(const kaiju_gpu_index *ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(g_acc_mutex);
+  return ix->acc_ready ? ix->acc_bytes : 0;
+}
+
+// the inputs of the passes that come from the context and its index; everything else is the caller's
+static int fv_job(kaiju_gpu_ctx *ctx, int paired, kjv::Job &J) {
+  if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup are not made on the device");
+  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
+  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
+  {
+    std::lock_guard<std::mutex> lk(g_acc_mutex);
+    if (!ctx->ix->acc_ready) return fail(KAIJU_GPU_ERR_ARG, "the index has no accession table on the device: call kaiju_gpu_index_upload_accessions() first");
+    J.acc_blob = ctx->ix->acc_blob; J.acc_off = ctx->ix->acc_off; J.acc_len = ctx->ix->acc_len; J.acc_rank = ctx->ix->acc_rank;
+  }
+  J.nseq = (uint32_t)ctx->ix->names.size();
+  J.P.db_length = ctx->ix->info.db_length;
+  J.P.min_evalue = ctx->params.min_evalue;
+  J.P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
+  J.P.protein = ctx->params.input_is_protein ? 1 : 0;
+  J.P.paired = paired ? 1 : 0;
+  J.pw = static_cast<const double *>(ctx->fmt_pw.p);
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_format_verbose_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *d_hits, const kaiju_gpu_compact *d_recs,
+                                               const uint64_t *d_off, uint32_t n, int paired, const uint32_t *d_n_acc,
+                                               const uint32_t *d_acc_iseq, const uint64_t *d_text_pos, const uint32_t *d_text_len,
+                                               const void *d_pep, uint32_t text_cap, const void *d_names_text, uint64_t names_bytes,
+                                               const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
+                                               kaiju_gpu_format_verbose_info *d_info, void *stream) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_verbose()) return rc;
+  if (!ctx || !d_info || (!d_out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if ((uintptr_t)d_out & 15) return fail(KAIJU_GPU_ERR_ARG, "the output pointer must be 16-byte aligned");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjv::Job J{};
+  if (int rc = fv_job(ctx, paired, J)) return rc;
+  J.hits = d_hits; J.recs = d_recs; J.off = d_off; J.n_acc = d_n_acc; J.acc_iseq = d_acc_iseq; J.text_pos = d_text_pos; J.text_len = d_text_len;
+  J.pep = static_cast<const uint8_t *>(d_pep); J.text_cap = text_cap; J.names_text = static_cast<const uint8_t *>(d_names_text);
+  J.names_bytes = names_bytes; J.names = d_names;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const char *err = "";
+  int rc = kj_fv_lengths(&ctx->format_v, s, J, n, &err);
+  if (rc) return fail(rc, err);
+  rc = kj_fv_write(ctx->format_v, s, d_out, out_cap, d_info, &err);
+  return rc ? fail(rc, err) : KAIJU_GPU_OK;
+  });
+}
+
+// *info and the bytes the passes wrote, from ctx->fv_info / fv_out to the host; blocks
+static int fv_download(kaiju_gpu_ctx *ctx, hipStream_t s, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info) {
+  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  uint64_t written = info->text_bytes;
+  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fv_written(ctx->format_v), sizeof written, hipMemcpyDeviceToHost));
+  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
+  if (written) KJ_HIP(hipMemcpy(out, ctx->fv_out.p, written, hipMemcpyDeviceToHost));
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_format_verbose(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hits, const kaiju_gpu_verbose *vout, const uint64_t *text_pos,
+                                        const char *text, uint64_t text_bytes, uint32_t text_cap, const kaiju_gpu_compact *recs,
+                                        const uint64_t *off, uint32_t n, int paired, const char *names_text, uint64_t names_bytes,
+                                        const kaiju_gpu_name_span *names, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_verbose()) return rc;
+  if (!ctx || !info || (n && (!hits || !vout || !text_pos || !recs || !off || !names)) || (!text && text_bytes) || (!names_text && names_bytes) ||
+      (!out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "the names must be below 2^32 - 32 bytes, a batch below 2^31 records");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjv::Job J{};
+  int rc;
+  if ((rc = fv_job(ctx, paired, J))) return rc;
+  // the arrays of the device form from the records of kaiju_gpu_classify_batch_verbose_packed
+  std::vector<uint32_t> nacc((size_t)n + 1), tlen((size_t)n + 1), trunc((size_t)n + 1), acc((size_t)n * kVbAcc + 1);
+  for (uint32_t r = 0; r < n; r++) {
+    const kaiju_gpu_verbose &v = vout[r];
+    nacc[r] = v.n_acc; tlen[r] = v.text_len; trunc[r] = v.truncated ? 1u : 0u;
+    memcpy(&acc[(size_t)r * kVbAcc], v.acc_iseq, sizeof v.acc_iseq);
+    const uint64_t w = std::min(v.text_len, text_cap);
+    if (text_pos[r] > text_bytes || w > text_bytes - text_pos[r]) return fail(KAIJU_GPU_ERR_ARG, "the peptides of a record lie outside the text");
+  }
+  static_assert(kVbAcc == KAIJU_GPU_MAX_ACC, "rows of the accession array");
+  if ((rc = ensure(ctx->h_hits, ((size_t)n + 1) * sizeof(kaiju_gpu_hit)))) return rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(ctx->vb_nacc, ((size_t)n + 1) * 4))) return rc;
+  if ((rc = ensure(ctx->vb_tlen, ((size_t)n + 1) * 4))) return rc;
+  if ((rc = ensure(ctx->fv_trunc, ((size_t)n + 1) * 4))) return rc;
+  if ((rc = ensure(ctx->vb_acc, (size_t)n * kVbAcc * 4 + 16))) return rc;
+  if ((rc = ensure(ctx->vb_pos, ((size_t)n + 1) * 8 + 16))) return rc;
+  if ((rc = ensure(ctx->vb_packed, text_bytes + 16))) return rc;
+  if ((rc = ensure(ctx->ing_text1, names_bytes + 64))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->fv_out, out_cap + 64))) return rc;
+  if ((rc = ensure(ctx->fv_info, sizeof(kaiju_gpu_format_verbose_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (names_bytes) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, names_text, names_bytes, hipMemcpyHostToDevice, s));
+  if (text_bytes) KJ_HIP(hipMemcpyAsync(ctx->vb_packed.p, text, text_bytes, hipMemcpyHostToDevice, s));
+  if (n) {
+    KJ_HIP(hipMemcpyAsync(ctx->h_hits.p, hits, (size_t)n * sizeof(kaiju_gpu_hit), hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->h_compact.p, recs, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->vb_nacc.p, nacc.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->vb_tlen.p, tlen.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->fv_trunc.p, trunc.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->vb_acc.p, acc.data(), (size_t)n * kVbAcc * 4, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->vb_pos.p, text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+  }
+  J.hits = static_cast<const kaiju_gpu_hit *>(ctx->h_hits.p); J.recs = static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p);
+  J.off = static_cast<const uint64_t *>(ctx->h_off.p); J.n_acc = static_cast<const uint32_t *>(ctx->vb_nacc.p);
+  J.acc_iseq = static_cast<const uint32_t *>(ctx->vb_acc.p); J.text_pos = static_cast<const uint64_t *>(ctx->vb_pos.p);
+  J.text_len = static_cast<const uint32_t *>(ctx->vb_tlen.p); J.trunc = static_cast<const uint32_t *>(ctx->fv_trunc.p);
+  J.pep = static_cast<const uint8_t *>(ctx->vb_packed.p); J.text_cap = text_cap;
+  J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
+  J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
+  const char *err = "";
+  rc = kj_fv_lengths(&ctx->format_v, s, J, n, &err);
+  if (rc == 0) rc = kj_fv_write(ctx->format_v, s, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
+  // (the host arrays above are pageable: the copies have left them when hipMemcpyAsync returns)
+  if (rc) { (void)hipStreamSynchronize(s); return fail(rc, err); }
+  return fv_download(ctx, s, out, out_cap, info);
+  });
+}
+
+extern "C" int kaiju_gpu_classify_batch_verbose_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *seqs, const uint64_t *off,
+                                                     uint32_t n_reads, int paired, const char *names_text, uint64_t names_bytes,
+                                                     const kaiju_gpu_name_span *names, const char **text, uint64_t *text_bytes,
+                                                     kaiju_gpu_format_verbose_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_verbose()) return rc;
+  if (!ctx || !t || !off || !text || !text_bytes || !info || (n_reads && !names) || (!names_text && names_bytes)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
+  if (names_bytes > kjf::kMaxBytes || n_reads > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "the names must be below 2^32 - 32 bytes, a batch below 2^31 records");
+  *text = nullptr; *text_bytes = 0;
+  memset(info, 0, sizeof *info);
+  if (n_reads == 0) return KAIJU_GPU_OK;
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjv::Job J{};
+  int rc;
+  if ((rc = fv_job(ctx, paired, J))) return rc;
+  if ((rc = ensure(ctx->ing_text1, names_bytes + 64))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n_reads + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)n_reads + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if ((rc = ensure(ctx->fv_info, sizeof(kaiju_gpu_format_verbose_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (names_bytes) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, names_text, names_bytes, hipMemcpyHostToDevice, s));
+  KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n_reads * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+  if ((rc = verbose_queue(ctx, seqs, off, n_reads, paired))) return rc;
+  hipLaunchKernelGGL(k_lca, dim3((n_reads + 255) / 256), dim3(256), 0, s, t->dev, reinterpret_cast<const Hit *>(ctx->h_hits.p), n_reads,
+                     reinterpret_cast<CompactHit *>(ctx->h_compact.p));
+  KJ_HIP(hipGetLastError());
+  J.hits = static_cast<const kaiju_gpu_hit *>(ctx->h_hits.p); J.recs = static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p);
+  J.off = static_cast<const uint64_t *>(ctx->h_off.p); J.n_acc = static_cast<const uint32_t *>(ctx->vb_nacc.p);
+  J.acc_iseq = static_cast<const uint32_t *>(ctx->vb_acc.p); J.text_pos = static_cast<const uint64_t *>(ctx->vb_pos.p);
+  J.text_len = static_cast<const uint32_t *>(ctx->vb_tlen.p); J.trunc = nullptr;
+  J.pep = static_cast<const uint8_t *>(ctx->vb_packed.p); J.text_cap = ctx->vb_text_cap;
+  J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
+  J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
+  const char *err = "";
+  if ((rc = kj_fv_lengths(&ctx->format_v, s, J, n_reads, &err))) return fail(rc, err);
+  // the one wait inside: the size of the text, so that the output can be sized
+  uint64_t total = 0;
+  KJ_HIP(hipMemcpyAsync(&total, kj_fv_total(ctx->format_v), sizeof total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  call_mark("verbose text: size of the text on the host");
+  // (a line is its name and at most: "C\t" "\t" two numbers, 21 ids, 20 prefixes, the peptides, the tabs)
+  if (total > names_bytes + (uint64_t)n_reads * (512 + 20ull * (kjv::kMaxPrefix + 1) + ctx->vb_text_cap)) return fail(KAIJU_GPU_ERR_HIP, "the format passes report an impossible size");
+  if ((rc = ensure(ctx->fv_out, total + 64))) return rc;
+  if (ctx->vb_host.size() < total) ctx->vb_host.resize((size_t)total);
+  if ((rc = kj_fv_write(ctx->format_v, s, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
+  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  if (total) KJ_HIP(hipMemcpyAsync(ctx->vb_host.data(), ctx->fv_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  if (info->text_bytes != total || info->overflow) return fail(KAIJU_GPU_ERR_HIP, "the format passes wrote another size than they announced");
+  *text = reinterpret_cast<const char *>(ctx->vb_host.data());
+  *text_bytes = total;
   return KAIJU_GPU_OK;
   });
 }

@@ -806,7 +806,7 @@ int main(int argc, char **argv) {
   // page-faulting) it for every batch
   mallopt(M_MMAP_THRESHOLD, 1 << 30);
   mallopt(M_TRIM_THRESHOLD, 1 << 30);
-  std::atomic<uint64_t> inexact_batches{0}, inexact_reads{0};
+  std::atomic<uint64_t> inexact_batches{0}, inexact_reads{0}, truncated_reads{0};
   kaiju_gpu_params params;
   kaiju_gpu_default_params(&params, 1);
   std::string nodes_fn, fmi_fn, in1_fn, in2_fn, out_fn;
@@ -871,6 +871,12 @@ int main(int argc, char **argv) {
   const bool device_output = output_env && !strcmp(output_env, "device") && device_ingest;
   if (output_env && !strcmp(output_env, "device") && !device_output)
     fprintf(stderr, "KAIJU_GPU_OUTPUT=device is ignored: it needs KAIJU_GPU_INGEST=device and the three-column output of kaiju / kaiju-multi without -v\n");
+  // KAIJU_GPU_VERBOSE_OUTPUT=device: with -v the device writes the seven-column lines (format_verbose.hip) and every piece of a
+  // batch comes back as finished text.  kaiju / kaiju-multi only; ingest stays on the host.
+  const char *vout_env = getenv("KAIJU_GPU_VERBOSE_OUTPUT");
+  const bool device_vout = vout_env && !strcmp(vout_env, "device") && verbose && !xmode && !parse_only;
+  if (vout_env && !strcmp(vout_env, "device") && (xmode || parse_only))
+    fprintf(stderr, "KAIJU_GPU_VERBOSE_OUTPUT=device is ignored: it applies to the -v output of kaiju / kaiju-multi\n");
   if (verbose) fprintf(stderr, "%s Reading database\n", now().c_str());
   // Which GPUs: KAIJU_GPU_DEVICE=<n> (one, default 0) or KAIJU_GPU_DEVICES=<n,n,...|all>: the index is replicated on each of
   // them (parsed and packed once), input block b goes to context b mod (2 x GPUs) - SURVEY 8e's "block b to GPU b mod N" -
@@ -936,10 +942,15 @@ int main(int argc, char **argv) {
     if (rc != 0) die(std::string("Could not load ") + fmi_fn + ": " + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
     kaiju_gpu_index_get_info(index, &info);
     if (info.warnings && verbose) fprintf(stderr, " Warning: the index triggers a latent bug of the reference (flags %u)\n", info.warnings);
-    if (!verbose && !xmode)
+    if ((!verbose || device_vout) && !xmode)
       for (int d = 0; d < n_dev; d++) {
         rc = kaiju_gpu_taxonomy_upload(tax, devices[(size_t)d], &dtaxes[(size_t)d]);
         if (rc != 0) die(std::string("kaiju_gpu_taxonomy_upload: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
+      }
+    if (device_vout)
+      for (int d = 0; d < n_dev; d++) {                    // (every replica: column 6 is made where the batch runs)
+        rc = kaiju_gpu_index_upload_accessions(indexes[(size_t)d]);
+        if (rc != 0) die(std::string("kaiju_gpu_index_upload_accessions: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
       }
     for (int k = 0; k < n_ctx; k++) {          // contexts 2d and 2d + 1 live on GPU d
       rc = kaiju_gpu_create(&ctx[(size_t)k], indexes[(size_t)(k / 2)], &params);
@@ -1083,10 +1094,13 @@ int main(int argc, char **argv) {
           uint64_t piece_error_flags = 0;
           uint64_t device_inexact = 0;
           if (verbose) {
-            b->hits.resize(n);
-            b->vrec.resize(n);
-            b->vpos.resize(n);
+            if (!device_vout) {
+              b->hits.resize(n);
+              b->vrec.resize(n);
+              b->vpos.resize(n);
+            }
             std::vector<uint64_t> poff;
+            std::vector<kaiju_gpu_name_span> pspans;
             piece_error_flags = 0;
             for (uint32_t lo = 0; lo < n && r == 0;) {
               // the longest piece from read lo on whose text fits the budget (at least one read)
@@ -1108,6 +1122,25 @@ int main(int argc, char **argv) {
               }
               const char *ptext = nullptr;
               uint64_t pbytes = 0;
+              if (device_vout) {
+                // the piece's names go up with it, the finished lines come back (kaiju_gpu_classify_batch_verbose_text)
+                const uint32_t nbase = b->name_off[lo];
+                pspans.resize(pn);
+                for (uint32_t q = 0; q < pn; q++) { pspans[q].pos = b->name_off[lo + q] - nbase; pspans[q].len = b->name_off[lo + q + 1] - b->name_off[lo + q]; }
+                kaiju_gpu_format_verbose_info fi;
+                memset(&fi, 0, sizeof fi);
+                r = kaiju_gpu_classify_batch_verbose_text(ctx[k], dtaxes[(size_t)(k / 2)], b->seqs.data() + base, po, pn, paired ? 1 : 0, b->names.data() + nbase,
+                                                          b->name_off[hi] - nbase, pspans.data(), &ptext, &pbytes, &fi);
+                if (r == 0) {
+                  if (fi.n_records != pn) die("internal error: the device formatted " + std::to_string(fi.n_records) + " records of " + std::to_string(pn));
+                  b->text.append(ptext, pbytes);
+                  device_inexact += (uint64_t)fi.n_inexact + fi.n_truncated;
+                  truncated_reads += fi.n_truncated;
+                }
+                { kaiju_gpu_stats ps; if (r == 0 && kaiju_gpu_get_stats(ctx[k], &ps) == 0) piece_error_flags |= ps.error_flags; }
+                lo = hi;
+                continue;
+              }
               r = kaiju_gpu_classify_batch_verbose_packed(ctx[k], b->seqs.data() + base, po, pn, paired ? 1 : 0, b->hits.data() + lo,
                                                           b->vrec.data() + lo, b->vpos.data() + lo, &ptext, &pbytes);
               if (r == 0) {
@@ -1120,6 +1153,7 @@ int main(int argc, char **argv) {
               { kaiju_gpu_stats ps; if (r == 0 && kaiju_gpu_get_stats(ctx[k], &ps) == 0) piece_error_flags |= ps.error_flags; }
               lo = hi;
             }
+            if (device_vout && r == 0) { b->text_done = true; n = 0; }     // (no records came back: nothing to look through below)
           } else if (xmode) {
             b->hits.resize(n);
             r = kaiju_gpu_classify_batch(ctx[k], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, b->hits.data());
@@ -1314,6 +1348,8 @@ int main(int argc, char **argv) {
       fprintf(stderr, "%s Processing input file %s%s%s\n", now().c_str(), list1[i].c_str(), paired ? " and " : "", paired ? list2[i].c_str() : "");
     run_sample(list1[i], paired ? list2[i] : std::string(), i < list_out.size() ? list_out[i] : std::string());
   }
+  // (the host formatter warns read by read; the device reports a count)
+  if (truncated_reads.load()) fprintf(stderr, "Warning: matched peptides of %llu reads truncated\n", (unsigned long long)truncated_reads.load());
   if (verbose) fprintf(stderr, "%s Finished.\n", now().c_str());
   if (getenv("KAIJU_GPU_STAGE_TIMES"))
     fprintf(stderr, "[CPU time per stage, summed over its threads] read %.3f s, parse %.3f s, gpu calls %.3f s, format %.3f s, "
