@@ -423,8 +423,8 @@ int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy
    (kaiju_amd/csrc/format.hip; the rules: kj_format.h): per record the decision of kaiju_finalize_compact (E-value gate
    included, bit for bit: the table argument is in kj_format.h) and the line "C\t<name>\t<taxon>\n" or "U\t<name>\t0\n", the
    name being text1[names[r].pos, + names[r].len); the lines of records 0 .. n - 1 follow each other in `out`.  Mode,
-   use_evalue, min_evalue and input_is_protein are the context's, db_length its index's.  -v, kaijux and kaijup lines are not
-   made here. */
+   use_evalue, min_evalue and input_is_protein are the context's, db_length its index's.  The lines of -v are made by the passes of
+   kaiju_gpu_format_verbose, those of kaijux and kaijup by the passes of kaiju_gpu_format_seq, both further down. */
 typedef struct kaiju_gpu_format_info {
   uint64_t text_bytes;             /* size of the whole text, whether or not it fitted                                      */
   uint32_t n_records, n_classified;/* records formatted (= n), 'C' lines among them                                         */
@@ -516,6 +516,53 @@ int kaiju_gpu_classify_batch_verbose_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_ta
                                           uint32_t n_reads, int paired, const char *names_text, uint64_t names_bytes,
                                           const kaiju_gpu_name_span *names, const char **text, uint64_t *text_bytes,
                                           kaiju_gpu_format_verbose_info *info);
+
+/* ---- the lines of kaijux / kaijup on the device: hits in, text out ------------------------------------------ */
+/* What stage 4 of the command line programs does on the host for kaijux / kaijup, with and without -v, as HIP passes
+   (kaiju_amd/csrc/format_seq.hip; the rules: kj_format_seq.h): the decision of the three-column lines on the record
+   {lca = n_ids ? 1 : 0, best, info = n_ids}; for a classified read "C\t<name>\t<best>\t<ids>\t<peptides>\n" - the names of the
+   matched database sequences in ascending order of their numbers, each followed by ',', and with -v the peptides as k_vb_pack
+   packs them -; for any other "U\t<name>\t0\n" if the read is gated and "U\t<name>\n" if not.  Which reads are gated is an
+   argument: */
+enum { KAIJU_GPU_U_RULE_NUCLEOTIDE = 0,  /* kaijux (with -p too): read 1 shorter than 3 x min_fragment_length, of a pair both mates */
+       KAIJU_GPU_U_RULE_PROTEIN = 1 };   /* kaijup: read 1 shorter than min_fragment_length, or without a run of amino-acid letters
+                                            of that length that (Greedy) scores min_score on the BLOSUM62 diagonal                */
+/* The names of all sequences of the index to its device: one blob, per sequence an offset (8 bytes) and a length (4).  Explicit
+   - a run that does not ask never pays for it - and idempotent; concurrent callers are serialised.  For indexes of either id
+   mode.  A name longer than 2^24 bytes: KAIJU_GPU_ERR_UNSUPPORTED. */
+int kaiju_gpu_index_upload_seq_names(kaiju_gpu_index *ix);
+/* bytes of the table in HBM (blob + 12 per sequence), 0 before the upload */
+uint64_t kaiju_gpu_index_seq_name_bytes(const kaiju_gpu_index *ix);
+/* All pointers are device pointers on the context's GPU.  d_hits: n hit records of a context whose index was loaded with
+   KAIJU_GPU_IDS_SEQUENCE (any other: KAIJU_GPU_ERR_ARG); d_off: 2n + 1; d_seqs: the reads d_off points into, looked at under
+   KAIJU_GPU_U_RULE_PROTEIN only (NULL otherwise); d_pep == NULL: no peptide column (without -v), d_text_pos / d_text_len /
+   text_cap are not looked at; else as in kaiju_gpu_format_verbose_device.  d_names_text / names_bytes / d_names / d_out /
+   out_cap / d_info / stream and the scratch (24 bytes per record and a shadow of out_cap bytes) as there: d_out 16-byte
+   aligned (KAIJU_GPU_ERR_ARG otherwise), asynchronous, nothing waits for the host.  Without an uploaded name table:
+   KAIJU_GPU_ERR_ARG. */
+int kaiju_gpu_format_seq_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *d_hits, const uint64_t *d_off, uint32_t n, int paired,
+                                int u_rule, const void *d_seqs, const uint64_t *d_text_pos, const uint32_t *d_text_len,
+                                const void *d_pep, uint32_t text_cap, const void *d_names_text, uint64_t names_bytes,
+                                const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
+                                kaiju_gpu_format_verbose_info *d_info, void *stream);
+/* The same with host pointers.  seqs: off[2n] bytes (NULL unless KAIJU_GPU_U_RULE_PROTEIN).  text == NULL: no peptide column,
+   vout and text_pos are not looked at; else vout[r].text_len letters at text + text_pos[r], cut at text_cap; a classified record
+   is counted as truncated when that happens or when vout[r].truncated is set.  Everything goes up, *info and the bytes written
+   come down; blocks.  out[0 .. out_cap): only the bytes of the lines written change. */
+int kaiju_gpu_format_seq(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hits, const uint64_t *off, uint32_t n, int paired, int u_rule,
+                         const char *seqs, const kaiju_gpu_verbose *vout, const uint64_t *text_pos, const char *text,
+                         uint64_t text_bytes, uint32_t text_cap, const char *names_text, uint64_t names_bytes,
+                         const kaiju_gpu_name_span *names, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info);
+/* Reads in, the text of kaijux / kaijup out, on the context's stream: without `verbose` the plain classification of
+   kaiju_gpu_classify_batch, with it the verbose classification and k_vb_pack as kaiju_gpu_classify_batch_verbose_text queues
+   them, then the passes above.  The one synchronisation inside is the read-back of the text's size in front of the write pass
+   (the library owns and sizes the output).  *text (text_bytes bytes) stays valid until the next verbose or text call on this
+   context.  No hit record, sequence number or peptide string crosses to the host.  A context whose index was not loaded with
+   KAIJU_GPU_IDS_SEQUENCE: KAIJU_GPU_ERR_ARG. */
+int kaiju_gpu_classify_batch_seq_text(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int paired,
+                                      int verbose, int u_rule, const char *names_text, uint64_t names_bytes,
+                                      const kaiju_gpu_name_span *names, const char **text, uint64_t *text_bytes,
+                                      kaiju_gpu_format_verbose_info *info);
 
 /* ---- several processes of a node, one per GPU: the gather --------------- */
 /* BASELINE north star: "reads shard embarrassingly across the GPUs of one node with the index replicated per GPU and per-GPU

@@ -166,6 +166,16 @@ def lib():
                                                C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_classify_batch_verbose_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                                             C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]
+    if hasattr(L, "kaiju_gpu_index_upload_seq_names"):        # (likewise)
+        L.kaiju_gpu_index_upload_seq_names.argtypes = [C.c_void_p]
+        L.kaiju_gpu_index_seq_name_bytes.restype = C.c_uint64
+        L.kaiju_gpu_index_seq_name_bytes.argtypes = [C.c_void_p]
+        L.kaiju_gpu_format_seq_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_format_seq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_classify_batch_seq_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -192,6 +202,7 @@ def device_count() -> int:
 
 
 IDS_TAXON, IDS_SEQUENCE = 0, 1     # kaiju_gpu_index_load_ex
+U_RULE_NUCLEOTIDE, U_RULE_PROTEIN = 0, 1     # KAIJU_GPU_U_RULE_*: which unclassified reads of kaijux / kaijup get a third column
 
 
 class Index:
@@ -249,6 +260,12 @@ class Index:
         returns its bytes in HBM"""
         _check(lib().kaiju_gpu_index_upload_accessions(self._h))
         return int(lib().kaiju_gpu_index_accession_bytes(self._h))
+
+    def upload_seq_names(self) -> int:
+        """kaiju_gpu_index_upload_seq_names: the names of all sequences to the device, for the lines of kaijux / kaijup (explicit,
+        idempotent); returns the table's bytes in HBM"""
+        _check(lib().kaiju_gpu_index_upload_seq_names(self._h))
+        return int(lib().kaiju_gpu_index_seq_name_bytes(self._h))
 
     def close(self):
         if self._h:
@@ -626,6 +643,63 @@ class Classifier:
         info = np.zeros(1, dtype=FORMAT_VERBOSE_INFO_DTYPE)
         _check(lib().kaiju_gpu_classify_batch_verbose_text(self._h, dtax._h, seqs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, nt.ctypes.data,
                                                            len(nt) - 1, names.ctypes.data, C.byref(text), C.byref(nbytes), info.ctypes.data))
+        return (C.string_at(text.value, nbytes.value) if nbytes.value else b""), info[0]
+
+    def format_seq(self, hits: np.ndarray, off: np.ndarray, names_text, names: np.ndarray, paired=False, u_rule=U_RULE_NUCLEOTIDE, seqs=None,
+                   v=None, text_pos=None, text=None, text_cap=0xffffffff, out_cap=None, out=None):
+        """hit records of sequence numbers, off[], the text the names lie in and the name spans to the lines of kaijux / kaijup
+        (kaiju_gpu_format_seq): host buffers, blocking.  seqs: the reads (U_RULE_PROTEIN only); text None: no peptide column, else
+        v (kaiju_gpu_verbose records), text_pos and the packed peptides as classify_verbose_packed returns them.  Returns (out,
+        info): out is a uint8 array of which the lines written have changed (out_cap bytes), info a FORMAT_VERBOSE_INFO_DTYPE
+        record.  Index.upload_seq_names() first."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        nt = np.frombuffer(bytes(names_text) + b"\0", dtype=np.uint8)
+        n = len(hits)
+        assert len(off) == 2 * n + 1 and len(names) == n
+        sq = None if seqs is None else np.frombuffer(bytes(seqs) + b"\0", dtype=np.uint8)
+        pep = None
+        if text is not None:
+            v = np.ascontiguousarray(v, dtype=VERBOSE_DTYPE)
+            text_pos = np.ascontiguousarray(text_pos, dtype=np.uint64)
+            pep = np.frombuffer(bytes(text) + b"\0", dtype=np.uint8)
+            assert len(v) == n and len(text_pos) == n
+        assert out_cap is not None or out is not None
+        cap = int(out_cap) if out_cap is not None else len(out)
+        if out is None:
+            out = np.zeros(cap + 1, dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) >= cap
+        info = np.zeros(1, dtype=FORMAT_VERBOSE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_format_seq(self._h, hits.ctypes.data, off.ctypes.data, n, 1 if paired else 0, int(u_rule), None if sq is None else sq.ctypes.data,
+                                          None if pep is None else v.ctypes.data, None if pep is None else text_pos.ctypes.data,
+                                          None if pep is None else pep.ctypes.data, 0 if pep is None else len(pep) - 1, int(text_cap), nt.ctypes.data,
+                                          len(nt) - 1, names.ctypes.data, out.ctypes.data, cap, info.ctypes.data))
+        return out, info[0]
+
+    def format_seq_device(self, d_hits_ptr: int, d_off_ptr: int, n: int, d_seqs_ptr: int, d_text_pos_ptr: int, d_text_len_ptr: int, d_pep_ptr: int,
+                          text_cap: int, d_names_text_ptr: int, names_bytes: int, d_names_ptr: int, d_out_ptr: int, out_cap: int, d_info_ptr: int,
+                          paired=False, u_rule=U_RULE_NUCLEOTIDE, stream: int = 0):
+        """the same for device-resident buffers (raw pointers; d_out 16-byte aligned; d_pep 0: no peptide column):
+        kaiju_gpu_format_seq_device, asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_format_seq_device(self._h, d_hits_ptr or None, d_off_ptr or None, n, 1 if paired else 0, int(u_rule), d_seqs_ptr or None,
+                                                 d_text_pos_ptr or None, d_text_len_ptr or None, d_pep_ptr or None, int(text_cap), d_names_text_ptr or None,
+                                                 names_bytes, d_names_ptr or None, d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def classify_seq_text(self, seqs: np.ndarray, off: np.ndarray, names_text, names: np.ndarray, paired=False, verbose=False, u_rule=U_RULE_NUCLEOTIDE):
+        """reads in, the lines of kaijux / kaijup out (kaiju_gpu_classify_batch_seq_text).  Returns (text as bytes - a copy, the
+        library's own is valid until the context's next verbose or text call -, a FORMAT_VERBOSE_INFO_DTYPE record)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        nt = np.frombuffer(bytes(names_text) + b"\0", dtype=np.uint8)
+        n = (len(off) - 1) // 2
+        assert len(names) == n
+        text = C.c_void_p()
+        nbytes = C.c_uint64()
+        info = np.zeros(1, dtype=FORMAT_VERBOSE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_classify_batch_seq_text(self._h, seqs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, 1 if verbose else 0, int(u_rule),
+                                                       nt.ctypes.data, len(nt) - 1, names.ctypes.data, C.byref(text), C.byref(nbytes), info.ctypes.data))
         return (C.string_at(text.value, nbytes.value) if nbytes.value else b""), info[0]
 
     OP_COUNT_NAMES = ("kmer_lookups", "update_si", "update_si_lines", "lf_steps", "lf_lines", "sa_samples", "read_meta",

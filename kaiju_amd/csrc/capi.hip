@@ -44,6 +44,7 @@
 #include "kj_ingest.h"
 #include "kj_format.h"
 #include "kj_format_verbose.h"
+#include "kj_format_seq.h"
 // Libraries linked from a source list of their own (the compile-time variants of tests/tools/mem_variants.sh: search lanes
 // only) need not hold ingest.hip: the two functions are weak references here, and without them the entry points below say
 // KAIJU_GPU_ERR_UNSUPPORTED.  kaiju_amd/build.py always links ingest.hip.
@@ -60,6 +61,12 @@ __attribute__((weak)) decltype(kj_fv_write) kj_fv_write;
 __attribute__((weak)) decltype(kj_fv_written) kj_fv_written;
 __attribute__((weak)) decltype(kj_fv_free) kj_fv_free;
 extern "C" __attribute__((weak)) decltype(kaiju_accession_ranks) kaiju_accession_ranks;
+// (format_seq.hip likewise)
+__attribute__((weak)) decltype(kj_fs_lengths) kj_fs_lengths;
+__attribute__((weak)) decltype(kj_fs_total) kj_fs_total;
+__attribute__((weak)) decltype(kj_fs_write) kj_fs_write;
+__attribute__((weak)) decltype(kj_fs_written) kj_fs_written;
+__attribute__((weak)) decltype(kj_fs_free) kj_fs_free;
 #ifdef KJ_GREEDY3                    // the experimental row-pool Greedy lane: variant builds only
 #include "kj_greedy3.h"
 #endif
@@ -1067,6 +1074,13 @@ struct kaiju_gpu_index {
   const uint32_t *acc_len = nullptr, *acc_rank = nullptr;
   uint64_t acc_bytes = 0;
   bool acc_ready = false;
+  // the sequence-name table (kaiju_gpu_index_upload_seq_names; the pointers are in `allocs`), read and written under g_sn_mutex
+  const uint8_t *sn_blob = nullptr;
+  const uint64_t *sn_off = nullptr;
+  const uint32_t *sn_len = nullptr;
+  uint64_t sn_bytes = 0;
+  uint32_t sn_max = 0;            // the longest name
+  bool sn_ready = false;
   ~kaiju_gpu_index() {
     (void)hipSetDevice(device);
     for (void *p : allocs) (void)hipFree(p);
@@ -1982,6 +1996,7 @@ struct kaiju_gpu_ctx {
   bool fmt_pw_ok = false;                              // (kjf::build_pow_table's verdict)
   kj_fv_scratch *format_v = nullptr;                   // the lines of -v (format_verbose.hip): lengths, offsets, the shadow
   DevBuf fv_out, fv_info, fv_trunc, fv_total;          // ... and the staging of its host-pointer entry points
+  kj_fs_scratch *format_s = nullptr;                   // the lines of kaijux / kaijup (format_seq.hip); staged in fv_out / fv_info / fv_trunc
   kaiju_gpu_stats stats{};
   uint32_t last_n = 0;
   uint32_t max_read_len = 1024;
@@ -1991,6 +2006,7 @@ struct kaiju_gpu_ctx {
     if (ingest) kj_ingest_free(ingest);
     if (format && kj_format_free) kj_format_free(format);
     if (format_v && kj_fv_free) kj_fv_free(format_v);
+    if (format_s && kj_fs_free) kj_fs_free(format_s);
     DevBuf *all[] = {&fv_out, &fv_info, &fv_trunc, &fv_total, &fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
                      &vb_nacc, &vb_acc, &vb_tlen, &vb_text, &vb_bestv, &vb_bestv_retry, &vb_packed, &vb_pos,
                      &redo_bitmap, &redo_list, &redo_items, &redo_index, &redo_pool, &redo_work, &redo_cls};
@@ -3259,6 +3275,247 @@ extern "C" int kaiju_gpu_classify_batch_verbose_text(kaiju_gpu_ctx *ctx, const k
   if ((rc = ensure(ctx->fv_out, total + 64))) return rc;
   if (ctx->vb_host.size() < total) ctx->vb_host.resize((size_t)total);
   if ((rc = kj_fv_write(ctx->format_v, s, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
+  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  if (total) KJ_HIP(hipMemcpyAsync(ctx->vb_host.data(), ctx->fv_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  if (info->text_bytes != total || info->overflow) return fail(KAIJU_GPU_ERR_HIP, "the format passes wrote another size than they announced");
+  *text = reinterpret_cast<const char *>(ctx->vb_host.data());
+  *text_bytes = total;
+  return KAIJU_GPU_OK;
+  });
+}
+
+// ---- the lines of kaijux / kaijup on the device (format_seq.hip) --------------------------------------------------
+static std::mutex g_sn_mutex;       // the sequence-name tables of all indexes: upload against upload, upload against the readers below
+static int no_format_seq() {
+  if (!kj_fs_lengths) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "this library was linked without format_seq.hip");
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_index_upload_seq_names(kaiju_gpu_index *ix) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_seq()) return rc;
+  if (!ix) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(g_sn_mutex);
+  if (ix->sn_ready) return KAIJU_GPU_OK;
+  const size_t nseq = ix->names.size();
+  if (nseq >= 0xffffffffull) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "more than 2^32 - 2 sequences");
+  std::vector<uint64_t> noff(nseq + 1);
+  std::vector<uint32_t> len(nseq + 1);
+  uint64_t total = 0;
+  uint32_t longest = 0;
+  for (size_t i = 0; i < nseq; i++) {
+    // (what kaiju_gpu_index_seq_name hands out: the name as a C string)
+    const size_t l = strlen(ix->names[i].c_str());
+    if (l > kjq::kMaxSeqName) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a sequence name of the index is longer than 2^24 bytes");
+    len[i] = (uint32_t)l; noff[i] = total; total += l;
+    longest = std::max(longest, len[i]);
+  }
+  noff[nseq] = total;
+  std::vector<uint8_t> blob((size_t)total + 1);
+  for (size_t i = 0; i < nseq; i++) if (len[i]) memcpy(blob.data() + noff[i], ix->names[i].c_str(), len[i]);
+  KJ_HIP(hipSetDevice(ix->device));
+  void *d[3] = {nullptr, nullptr, nullptr};
+  const void *src[3] = {blob.data(), noff.data(), len.data()};
+  const size_t bytes[3] = {(size_t)total + 1, (nseq + 1) * 8, (nseq + 1) * 4};
+  for (int k = 0; k < 3; k++) {
+    if (hipMalloc(&d[k], bytes[k] + 16) != hipSuccess || hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      for (int j = 0; j <= k; j++) if (d[j]) (void)hipFree(d[j]);
+      return fail(KAIJU_GPU_ERR_NOMEM, "the sequence-name table could not be uploaded");
+    }
+  }
+  for (int k = 0; k < 3; k++) ix->allocs.push_back(d[k]);
+  ix->sn_blob = static_cast<const uint8_t *>(d[0]); ix->sn_off = static_cast<const uint64_t *>(d[1]); ix->sn_len = static_cast<const uint32_t *>(d[2]);
+  ix->sn_bytes = total + 12 * (uint64_t)nseq;
+  ix->sn_max = longest;
+  ix->sn_ready = true;
+  return KAIJU_GPU_OK;
+  });
+}
+extern "C" uint64_t kaiju_gpu_index_seq_name_bytes(const kaiju_gpu_index *ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(g_sn_mutex);
+  return ix->sn_ready ? ix->sn_bytes : 0;
+}
+
+// the inputs of the passes that come from the context and its index; everything else is the caller's
+static int fs_job(kaiju_gpu_ctx *ctx, int paired, int u_rule, kjq::Job &J) {
+  if (ctx->ix->id_mode != KAIJU_GPU_IDS_SEQUENCE) return fail(KAIJU_GPU_ERR_ARG, "the lines of kaijux / kaijup need an index loaded with KAIJU_GPU_IDS_SEQUENCE");
+  if (u_rule != KAIJU_GPU_U_RULE_NUCLEOTIDE && u_rule != KAIJU_GPU_U_RULE_PROTEIN) return fail(KAIJU_GPU_ERR_ARG, "u_rule must be KAIJU_GPU_U_RULE_NUCLEOTIDE or KAIJU_GPU_U_RULE_PROTEIN");
+  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
+  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
+  {
+    std::lock_guard<std::mutex> lk(g_sn_mutex);
+    if (!ctx->ix->sn_ready) return fail(KAIJU_GPU_ERR_ARG, "the index has no sequence-name table on the device: call kaiju_gpu_index_upload_seq_names() first");
+    J.sn_blob = ctx->ix->sn_blob; J.sn_off = ctx->ix->sn_off; J.sn_len = ctx->ix->sn_len;
+  }
+  J.nseq = (uint32_t)ctx->ix->names.size();
+  J.P.db_length = ctx->ix->info.db_length;
+  J.P.min_evalue = ctx->params.min_evalue;
+  J.P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
+  J.P.protein = ctx->params.input_is_protein ? 1 : 0;
+  J.P.paired = paired ? 1 : 0;
+  J.pw = static_cast<const double *>(ctx->fmt_pw.p);
+  J.u_rule = (uint32_t)u_rule;
+  J.min_frag = ctx->params.min_fragment_length;
+  J.min_score = ctx->params.min_score;
+  J.greedy = ctx->params.mode == 0 ? 0u : 1u;
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_format_seq_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *d_hits, const uint64_t *d_off, uint32_t n, int paired,
+                                           int u_rule, const void *d_seqs, const uint64_t *d_text_pos, const uint32_t *d_text_len,
+                                           const void *d_pep, uint32_t text_cap, const void *d_names_text, uint64_t names_bytes,
+                                           const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
+                                           kaiju_gpu_format_verbose_info *d_info, void *stream) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_seq()) return rc;
+  if (!ctx || !d_info || (!d_out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if ((uintptr_t)d_out & 15) return fail(KAIJU_GPU_ERR_ARG, "the output pointer must be 16-byte aligned");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjq::Job J{};
+  if (int rc = fs_job(ctx, paired, u_rule, J)) return rc;
+  J.hits = d_hits; J.off = d_off; J.seqs = static_cast<const uint8_t *>(d_seqs);
+  J.pep = static_cast<const uint8_t *>(d_pep);
+  if (d_pep) { J.text_pos = d_text_pos; J.text_len = d_text_len; J.text_cap = text_cap; }
+  J.names_text = static_cast<const uint8_t *>(d_names_text); J.names_bytes = names_bytes; J.names = d_names;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const char *err = "";
+  int rc = kj_fs_lengths(&ctx->format_s, s, J, n, &err);
+  if (rc) return fail(rc, err);
+  rc = kj_fs_write(ctx->format_s, s, d_out, out_cap, d_info, &err);
+  return rc ? fail(rc, err) : KAIJU_GPU_OK;
+  });
+}
+
+extern "C" int kaiju_gpu_format_seq(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hits, const uint64_t *off, uint32_t n, int paired, int u_rule,
+                                    const char *seqs, const kaiju_gpu_verbose *vout, const uint64_t *text_pos, const char *text,
+                                    uint64_t text_bytes, uint32_t text_cap, const char *names_text, uint64_t names_bytes,
+                                    const kaiju_gpu_name_span *names, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_seq()) return rc;
+  if (!ctx || !info || (n && (!hits || !off || !names)) || (n && text && (!vout || !text_pos)) || (!names_text && names_bytes) || (!out && out_cap))
+    return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "the names must be below 2^32 - 32 bytes, a batch below 2^31 records");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjq::Job J{};
+  int rc;
+  if ((rc = fs_job(ctx, paired, u_rule, J))) return rc;
+  const bool scan = u_rule == KAIJU_GPU_U_RULE_PROTEIN;
+  uint64_t seq_bytes = 0;
+  for (uint64_t i = 0; i < 2 * (uint64_t)n; i++) if (off[i + 1] < off[i]) return fail(KAIJU_GPU_ERR_ARG, "offsets must be non-decreasing");
+  if (scan && n) { seq_bytes = off[2 * (uint64_t)n]; if (seq_bytes && !seqs) return fail(KAIJU_GPU_ERR_ARG, "seqs is NULL"); }
+  std::vector<uint32_t> tlen, trunc;
+  if (text) {
+    tlen.resize((size_t)n + 1); trunc.resize((size_t)n + 1);
+    for (uint32_t r = 0; r < n; r++) {
+      tlen[r] = vout[r].text_len; trunc[r] = vout[r].truncated ? 1u : 0u;
+      const uint64_t w = std::min(vout[r].text_len, text_cap);
+      if (text_pos[r] > text_bytes || w > text_bytes - text_pos[r]) return fail(KAIJU_GPU_ERR_ARG, "the peptides of a record lie outside the text");
+    }
+  }
+  if ((rc = ensure(ctx->h_hits, ((size_t)n + 1) * sizeof(kaiju_gpu_hit)))) return rc;
+  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(ctx->h_seqs, seq_bytes + 64))) return rc;
+  if ((rc = ensure(ctx->vb_tlen, ((size_t)n + 1) * 4))) return rc;
+  if ((rc = ensure(ctx->fv_trunc, ((size_t)n + 1) * 4))) return rc;
+  if ((rc = ensure(ctx->vb_pos, ((size_t)n + 1) * 8 + 16))) return rc;
+  if ((rc = ensure(ctx->vb_packed, text_bytes + 16))) return rc;
+  if ((rc = ensure(ctx->ing_text1, names_bytes + 64))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->fv_out, out_cap + 64))) return rc;
+  if ((rc = ensure(ctx->fv_info, sizeof(kaiju_gpu_format_verbose_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (names_bytes) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, names_text, names_bytes, hipMemcpyHostToDevice, s));
+  if (text && text_bytes) KJ_HIP(hipMemcpyAsync(ctx->vb_packed.p, text, text_bytes, hipMemcpyHostToDevice, s));
+  if (seq_bytes) KJ_HIP(hipMemcpyAsync(ctx->h_seqs.p, seqs, seq_bytes, hipMemcpyHostToDevice, s));
+  {
+    const uint64_t zero = 0;                             // (n = 0: off[0] is all there is)
+    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, n ? off : &zero, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+  }
+  if (n) {
+    KJ_HIP(hipMemcpyAsync(ctx->h_hits.p, hits, (size_t)n * sizeof(kaiju_gpu_hit), hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+    if (text) {
+      KJ_HIP(hipMemcpyAsync(ctx->vb_tlen.p, tlen.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+      KJ_HIP(hipMemcpyAsync(ctx->fv_trunc.p, trunc.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+      KJ_HIP(hipMemcpyAsync(ctx->vb_pos.p, text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    }
+  }
+  J.hits = static_cast<const kaiju_gpu_hit *>(ctx->h_hits.p); J.off = static_cast<const uint64_t *>(ctx->h_off.p);
+  J.seqs = scan ? static_cast<const uint8_t *>(ctx->h_seqs.p) : nullptr;
+  if (text) {
+    J.pep = static_cast<const uint8_t *>(ctx->vb_packed.p); J.text_cap = text_cap;
+    J.text_pos = static_cast<const uint64_t *>(ctx->vb_pos.p); J.text_len = static_cast<const uint32_t *>(ctx->vb_tlen.p);
+    J.trunc = static_cast<const uint32_t *>(ctx->fv_trunc.p);
+  }
+  J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
+  J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
+  const char *err = "";
+  rc = kj_fs_lengths(&ctx->format_s, s, J, n, &err);
+  if (rc == 0) rc = kj_fs_write(ctx->format_s, s, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
+  // (the host arrays above are pageable: the copies have left them when hipMemcpyAsync returns)
+  if (rc) { (void)hipStreamSynchronize(s); return fail(rc, err); }
+  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  uint64_t written = info->text_bytes;
+  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fs_written(ctx->format_s), sizeof written, hipMemcpyDeviceToHost));
+  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
+  if (written) KJ_HIP(hipMemcpy(out, ctx->fv_out.p, written, hipMemcpyDeviceToHost));
+  return KAIJU_GPU_OK;
+  });
+}
+
+extern "C" int kaiju_gpu_classify_batch_seq_text(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int paired,
+                                                 int verbose, int u_rule, const char *names_text, uint64_t names_bytes,
+                                                 const kaiju_gpu_name_span *names, const char **text, uint64_t *text_bytes,
+                                                 kaiju_gpu_format_verbose_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_seq()) return rc;
+  if (!ctx || !off || !text || !text_bytes || !info || (n_reads && !names) || (!names_text && names_bytes)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (names_bytes > kjf::kMaxBytes || n_reads > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "the names must be below 2^32 - 32 bytes, a batch below 2^31 records");
+  *text = nullptr; *text_bytes = 0;
+  memset(info, 0, sizeof *info);
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  kjq::Job J{};
+  int rc;
+  if ((rc = fs_job(ctx, paired, u_rule, J))) return rc;
+  if (n_reads == 0) return KAIJU_GPU_OK;
+  if ((rc = ensure(ctx->ing_text1, names_bytes + 64))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n_reads + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->fv_info, sizeof(kaiju_gpu_format_verbose_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (names_bytes) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, names_text, names_bytes, hipMemcpyHostToDevice, s));
+  KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n_reads * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+  uint32_t text_cap = 0;
+  if (verbose) {
+    if ((rc = verbose_queue(ctx, seqs, off, n_reads, paired))) return rc;
+    text_cap = ctx->vb_text_cap;
+    J.pep = static_cast<const uint8_t *>(ctx->vb_packed.p); J.text_cap = text_cap;
+    J.text_pos = static_cast<const uint64_t *>(ctx->vb_pos.p); J.text_len = static_cast<const uint32_t *>(ctx->vb_tlen.p);
+  } else if ((rc = classify_host_buffers(ctx, seqs, off, n_reads, paired))) return rc;
+  J.hits = static_cast<const kaiju_gpu_hit *>(ctx->h_hits.p); J.off = static_cast<const uint64_t *>(ctx->h_off.p);
+  J.seqs = static_cast<const uint8_t *>(ctx->h_seqs.p);
+  J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
+  J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
+  const char *err = "";
+  if ((rc = kj_fs_lengths(&ctx->format_s, s, J, n_reads, &err))) return fail(rc, err);
+  // the one wait inside: the size of the text, so that the output can be sized
+  uint64_t total = 0;
+  KJ_HIP(hipMemcpyAsync(&total, kj_fs_total(ctx->format_s), sizeof total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  call_mark("seq text: size of the text on the host");
+  // (a line is its name and at most: "C\t" "\t" a number, 21 names with their commas, the peptides, two tabs, "\n")
+  if (total > names_bytes + (uint64_t)n_reads * (64 + (uint64_t)kjq::kMaxIds * ((uint64_t)ctx->ix->sn_max + 1) + text_cap))
+    return fail(KAIJU_GPU_ERR_HIP, "the format passes report an impossible size");
+  if ((rc = ensure(ctx->fv_out, total + 64))) return rc;
+  if (ctx->vb_host.size() < total) ctx->vb_host.resize((size_t)total);
+  if ((rc = kj_fs_write(ctx->format_s, s, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
   KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
   if (total) KJ_HIP(hipMemcpyAsync(ctx->vb_host.data(), ctx->fv_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));

@@ -877,6 +877,12 @@ int main(int argc, char **argv) {
   const bool device_vout = vout_env && !strcmp(vout_env, "device") && verbose && !xmode && !parse_only;
   if (vout_env && !strcmp(vout_env, "device") && (xmode || parse_only))
     fprintf(stderr, "KAIJU_GPU_VERBOSE_OUTPUT=device is ignored: it applies to the -v output of kaiju / kaiju-multi\n");
+  // KAIJU_GPU_SEQ_OUTPUT=device: kaijux / kaijup, with or without -v: the device writes the lines (format_seq.hip) and every
+  // batch - with -v every piece of it - comes back as finished text.  Ingest stays on the host.
+  const char *sout_env = getenv("KAIJU_GPU_SEQ_OUTPUT");
+  const bool device_sout = sout_env && !strcmp(sout_env, "device") && xmode && !parse_only;
+  if (sout_env && !strcmp(sout_env, "device") && !xmode)
+    fprintf(stderr, "KAIJU_GPU_SEQ_OUTPUT=device is ignored: it applies to the output of kaijux / kaijup\n");
   if (verbose) fprintf(stderr, "%s Reading database\n", now().c_str());
   // Which GPUs: KAIJU_GPU_DEVICE=<n> (one, default 0) or KAIJU_GPU_DEVICES=<n,n,...|all>: the index is replicated on each of
   // them (parsed and packed once), input block b goes to context b mod (2 x GPUs) - SURVEY 8e's "block b to GPU b mod N" -
@@ -951,6 +957,11 @@ int main(int argc, char **argv) {
       for (int d = 0; d < n_dev; d++) {                    // (every replica: column 6 is made where the batch runs)
         rc = kaiju_gpu_index_upload_accessions(indexes[(size_t)d]);
         if (rc != 0) die(std::string("kaiju_gpu_index_upload_accessions: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
+      }
+    if (device_sout)
+      for (int d = 0; d < n_dev; d++) {                    // (every replica: the ids column is made where the batch runs)
+        rc = kaiju_gpu_index_upload_seq_names(indexes[(size_t)d]);
+        if (rc != 0) die(std::string("kaiju_gpu_index_upload_seq_names: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
       }
     for (int k = 0; k < n_ctx; k++) {          // contexts 2d and 2d + 1 live on GPU d
       rc = kaiju_gpu_create(&ctx[(size_t)k], indexes[(size_t)(k / 2)], &params);
@@ -1094,7 +1105,7 @@ int main(int argc, char **argv) {
           uint64_t piece_error_flags = 0;
           uint64_t device_inexact = 0;
           if (verbose) {
-            if (!device_vout) {
+            if (!device_vout && !device_sout) {
               b->hits.resize(n);
               b->vrec.resize(n);
               b->vpos.resize(n);
@@ -1122,15 +1133,20 @@ int main(int argc, char **argv) {
               }
               const char *ptext = nullptr;
               uint64_t pbytes = 0;
-              if (device_vout) {
-                // the piece's names go up with it, the finished lines come back (kaiju_gpu_classify_batch_verbose_text)
+              if (device_vout || device_sout) {
+                // the piece's names go up with it, the finished lines come back (kaiju_gpu_classify_batch_verbose_text, for
+                // kaijux / kaijup kaiju_gpu_classify_batch_seq_text)
                 const uint32_t nbase = b->name_off[lo];
                 pspans.resize(pn);
                 for (uint32_t q = 0; q < pn; q++) { pspans[q].pos = b->name_off[lo + q] - nbase; pspans[q].len = b->name_off[lo + q + 1] - b->name_off[lo + q]; }
                 kaiju_gpu_format_verbose_info fi;
                 memset(&fi, 0, sizeof fi);
-                r = kaiju_gpu_classify_batch_verbose_text(ctx[k], dtaxes[(size_t)(k / 2)], b->seqs.data() + base, po, pn, paired ? 1 : 0, b->names.data() + nbase,
-                                                          b->name_off[hi] - nbase, pspans.data(), &ptext, &pbytes, &fi);
+                if (device_sout)
+                  r = kaiju_gpu_classify_batch_seq_text(ctx[k], b->seqs.data() + base, po, pn, paired ? 1 : 0, 1, pmode ? KAIJU_GPU_U_RULE_PROTEIN : KAIJU_GPU_U_RULE_NUCLEOTIDE,
+                                                        b->names.data() + nbase, b->name_off[hi] - nbase, pspans.data(), &ptext, &pbytes, &fi);
+                else
+                  r = kaiju_gpu_classify_batch_verbose_text(ctx[k], dtaxes[(size_t)(k / 2)], b->seqs.data() + base, po, pn, paired ? 1 : 0, b->names.data() + nbase,
+                                                            b->name_off[hi] - nbase, pspans.data(), &ptext, &pbytes, &fi);
                 if (r == 0) {
                   if (fi.n_records != pn) die("internal error: the device formatted " + std::to_string(fi.n_records) + " records of " + std::to_string(pn));
                   b->text.append(ptext, pbytes);
@@ -1153,7 +1169,24 @@ int main(int argc, char **argv) {
               { kaiju_gpu_stats ps; if (r == 0 && kaiju_gpu_get_stats(ctx[k], &ps) == 0) piece_error_flags |= ps.error_flags; }
               lo = hi;
             }
-            if (device_vout && r == 0) { b->text_done = true; n = 0; }     // (no records came back: nothing to look through below)
+            if ((device_vout || device_sout) && r == 0) { b->text_done = true; n = 0; }     // (no records came back: nothing to look through below)
+          } else if (xmode && device_sout) {
+            // the names go up with the reads, the finished lines come back (kaiju_gpu_classify_batch_seq_text)
+            std::vector<kaiju_gpu_name_span> spans(n);
+            for (uint32_t q = 0; q < n; q++) { spans[q].pos = b->name_off[q]; spans[q].len = b->name_off[q + 1] - b->name_off[q]; }
+            const char *btext = nullptr;
+            uint64_t bbytes = 0;
+            kaiju_gpu_format_verbose_info fi;
+            memset(&fi, 0, sizeof fi);
+            r = kaiju_gpu_classify_batch_seq_text(ctx[k], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, 0, pmode ? KAIJU_GPU_U_RULE_PROTEIN : KAIJU_GPU_U_RULE_NUCLEOTIDE,
+                                                  b->names.data(), n ? b->name_off[n] : 0, spans.data(), &btext, &bbytes, &fi);
+            if (r == 0) {
+              if (fi.n_records != n) die("internal error: the device formatted " + std::to_string(fi.n_records) + " records of " + std::to_string(n));
+              b->text.assign(btext ? btext : "", bbytes);
+              b->text_done = true;
+              device_inexact = fi.n_inexact;
+              n = 0;                                    // (no records came back: nothing to look through below)
+            }
           } else if (xmode) {
             b->hits.resize(n);
             r = kaiju_gpu_classify_batch(ctx[k], b->seqs.data(), b->off.data(), n, paired ? 1 : 0, b->hits.data());
