@@ -180,7 +180,7 @@ int kaiju_gpu_index_get_info(const kaiju_gpu_index *ix, kaiju_gpu_index_info *in
    and packed on the device (KAIJU_GPU_FMI_STREAM) - can be compared array by array at any size.  out[]: [0] rank blocks,
    [1] count bases, [2] sampled sequence numbers, [3] taxon ids of the samples, [4] terminator rows, [5] taxon id and [6]
    validity per sequence, [7] k-mer table, [8] k-mer lines, [9] text, [10] full suffix array / 40-bit text positions,
-   [11] dense taxon index of every row (row_tax), [12] k (letters of the k-mer table), [13] C[] ; 0 for an array the index
+   [11] dense taxon index of every row (row_tax) or - kaiju_gpu_index_layout.row_tax_shift > 0 - of every 2^shift-th row, [12] k (letters of the k-mer table), [13] C[] ; 0 for an array the index
    does not have. */
 #define KAIJU_GPU_N_DIGESTS 14
 int kaiju_gpu_index_digest(const kaiju_gpu_index *ix, uint64_t *out, uint32_t n_out);
@@ -209,7 +209,8 @@ typedef struct kaiju_gpu_index_layout {
   uint32_t n_dense;             /* entries of tax_of_dense                                                                 */
   uint32_t beyond_lo, beyond_n, beyond_row;   /* KAIJU_IDX_WARN_SA_SHORT: text positions / a row behind the missing sample */
   uint32_t wide;                /* 1 = 64-bit positions (count bases, 16-byte k-mer entries)                               */
-  uint32_t reserved;
+  uint32_t row_tax_shift;       /* 0: array 11 is the table of every row, or absent; 1 .. 3: it is the SAMPLED table - entry i = */
+                                /* the dense taxon index of row i << row_tax_shift, ((bwtlen >> shift) + 1) * 4 + 64 bytes        */
 } kaiju_gpu_index_layout;
 int kaiju_gpu_index_get_layout(const kaiju_gpu_index *ix, kaiju_gpu_index_layout *out);
 int kaiju_gpu_index_read_array(const kaiju_gpu_index *ix, uint32_t which, uint64_t offset_bytes, uint64_t n_bytes, void *host_out);
@@ -228,7 +229,8 @@ typedef struct kaiju_gpu_index_footprint {
   uint64_t text;          /* the database text (indexes that leave room for it: text verification of long matches)       */
   uint64_t sa_full;       /* ... and position + taxon of every row's suffix, 2 x 4 bytes per row (narrow indexes), or     */
                           /* the 40-bit text position of every 2^s-th row (wide indexes: s = 0 .. 3 by the room left)     */
-                          /* + the taxon of every row, 4 bytes each (wide indexes that leave room: KAIJU_GPU_ROW_TAX)     */
+                          /* + the taxon of every row, 4 bytes each (wide indexes that leave room: KAIJU_GPU_ROW_TAX), or  */
+                          /* of every 2^s-th row where only that fits (s = 1 .. 3, KAIJU_GPU_ROW_TAX_SHIFT)               */
   uint64_t other;         /* constant tables                                                                              */
   uint64_t total;
   uint32_t kmer_k, wide;  /* k of the k-mer lines (narrow: a five-letter table stays next to them) or of the table; 1 = 64-bit positions */
@@ -304,6 +306,23 @@ typedef struct {
 int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *off, uint32_t n_reads, int exact,
                           kaiju_gpu_seg_fragment *frags, uint64_t frag_cap, uint64_t *n_frags,
                           int32_t *lr, uint64_t lr_cap, uint64_t *n_lr);
+
+/* Diagnostics: the locate by itself.  Record r is given the suffix-array intervals first[r] .. first[r + 1] - 1 (at most 16:
+   rows lo[i] .. lo[i] + len[i] - 1, len[i] >= 1) as the matches a search lane would have left in it, and the call runs the
+   locate that a classification of this context would run on this index (the row -> taxon table, the sampled one, or the walk
+   to the suffix array's sample) over them: out[r] holds the ids of those rows in the reference's order (ids_from_SI: rows in
+   order, the limit max_match_ids tested in front of every row, first seen first) and KAIJU_HIT_ID_CAP where the limit ended
+   the traversal.  An interval that leaves the index (or, on an index with 32-bit positions, one whose length does not fit the
+   record), a record of more than 16 intervals and a call with more than KAIJU_GPU_LOCATE_MAX_RECORDS records give
+   KAIJU_GPU_ERR_ARG.  first[0] must be 0.  The call blocks.  It lets a test meet every alignment of an interval against the
+   samples without a read that produces it.  Where a classification would finish its records in the fused post-search pass (MEM
+   on an index with 32-bit positions and the row -> taxon table) the call runs k_mem_locate + k_mem_locate_list, the stand-alone
+   kernels of the same locate (what KAIJU_GPU_FUSED_POST=0 runs); a context whose search lanes walk to their ids themselves
+   (KAIJU_GPU_MEM_LANE=v1 and the like) has no locate kernel: KAIJU_GPU_ERR_UNSUPPORTED. */
+#define KAIJU_GPU_LOCATE_MAX_INTERVALS 16
+#define KAIJU_GPU_LOCATE_MAX_RECORDS (1u << 24)
+int kaiju_gpu_locate_intervals(kaiju_gpu_ctx *ctx, const uint64_t *lo, const uint32_t *len, const uint32_t *first,
+                               uint32_t n_records, kaiju_gpu_hit *out);
 
 /* ---- host side of the seam ------------------------------------------- */
 int kaiju_taxonomy_load(const char *nodes_dmp_path, kaiju_taxonomy **out);

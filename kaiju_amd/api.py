@@ -51,7 +51,7 @@ class IndexLayout(C.Structure):           # kaiju_gpu_index_layout
     _fields_ = [("bytes", C.c_uint64 * len(INDEX_ARRAYS)), ("C", C.c_uint64 * 22), ("bwtlen", C.c_uint64), ("n_sa", C.c_uint64),
                 ("sa_skip", C.c_uint64)] + [(k, C.c_uint32) for k in
                                             ("nseq", "chpt_exp", "mb_shift", "kmer_k", "kline_k", "tv_shift", "n_dense",
-                                             "beyond_lo", "beyond_n", "beyond_row", "wide", "reserved")]
+                                             "beyond_lo", "beyond_n", "beyond_row", "wide", "row_tax_shift")]
 
 
 class Stats(C.Structure):
@@ -255,6 +255,12 @@ class Index:
         _check(L.kaiju_gpu_index_read_array(self._h, which, offset, n_bytes, out.ctypes.data))
         return out
 
+    @property
+    def row_tax_shift(self) -> int:
+        """0: the row -> taxon table of this index holds every row (or there is none); s = 1 .. 3: it holds every 2^s-th row
+        (wide indexes too big for the full table, KAIJU_GPU_ROW_TAX_SHIFT)"""
+        return int(self.layout().row_tax_shift)
+
     def upload_accessions(self) -> int:
         """kaiju_gpu_index_upload_accessions: the accession table of column 6 of kaiju -v to the device (explicit, idempotent);
         returns its bytes in HBM"""
@@ -377,6 +383,21 @@ class Classifier:
         hits = np.zeros(n, dtype=HIT_DTYPE)
         _check(lib().kaiju_gpu_classify_batch(self._h, seqs.ctypes.data, off.ctypes.data, n,
                                               1 if paired else 0, hits.ctypes.data))
+        return hits
+
+    def locate_intervals(self, lo, length, first) -> np.ndarray:
+        """kaiju_gpu_locate_intervals (diagnostics): record r is given the suffix-array intervals first[r] .. first[r+1]-1 (rows
+        lo[i] .. lo[i] + length[i] - 1, at most 16 a record) as pending matches; the locate this context's classification would
+        run turns them into ids.  Returns the hit records (n_ids, taxid, KAIJU_HIT_ID_CAP in flags)."""
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint32)
+        first = np.ascontiguousarray(first, dtype=np.uint32)
+        n = len(first) - 1
+        assert n >= 0 and len(lo) == len(length) and (n == 0 or int(first[-1]) <= len(lo))
+        L = lib()
+        L.kaiju_gpu_locate_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        hits = np.zeros(n, dtype=HIT_DTYPE)
+        _check(L.kaiju_gpu_locate_intervals(self._h, lo.ctypes.data, length.ctypes.data, first.ctypes.data, n, hits.ctypes.data))
         return hits
 
     def set_max_read_length(self, n: int):

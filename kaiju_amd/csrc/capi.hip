@@ -39,6 +39,7 @@
 #include "host_tables.h"
 #include "kj_core.h"
 #include "kj_flow.h"
+#include "kj_rowtax_plan.h"
 #include "taxonomy.h"
 #include "exact_pass.h"
 #include "kj_ingest.h"
@@ -525,6 +526,16 @@ k_mem_locate_team(DevIndex ix, Params p, Batch b) {
   TeamWave<kLocTeam> team;
   mem_locate_read_team<false, kLocTeam>(ix, p, b.hits + r, team);
 }
+// Wide indexes with the SAMPLED row -> taxon table (DevIndex::row_tax_s): the same teams, every walk ends at the first row that is
+// a multiple of 2^rts_shift - 2^rts_shift - 1 LF steps on average and one load of the table where k_mem_locate_wide takes
+// 2^chpt_exp - 1 and two loads (sa_iseq, seq_taxid); row by row never more steps than that walk
+__global__ void __launch_bounds__(256)
+k_mem_locate_sampled(DevIndex ix, Params p, Batch b) {
+  const uint32_t r = (blockIdx.x * 256 + threadIdx.x) / kLocTeam;
+  if (r >= b.n_reads) return;
+  TeamWave<kLocTeam> team;
+  mem_locate_read_team<true, kLocTeam, true>(ix, p, b.hits + r, team);
+}
 // the same kernel under a second name for the second search of the lazy SEG flow (the few reads whose fragments SEG had
 // to cut), so that a kernel trace lists the full-size launches of k_mem by themselves
 __global__ void __launch_bounds__(kBlock, KJ_MEM_WAVES)
@@ -951,9 +962,10 @@ k_seq_walk_len(DevIndex ix, uint32_t *next, uint32_t *__restrict__ t_seq, uint32
 __global__ void __launch_bounds__(256)
 k_seq_walk_fill(DevIndex ix, uint32_t *next, const uint32_t *__restrict__ t_seq, const uint32_t *__restrict__ len, const uint64_t *__restrict__ off,
                 uint8_t *__restrict__ text, uint8_t *__restrict__ tpos5, uint32_t tv_shift,
-                uint32_t *__restrict__ row_tax, const uint32_t *__restrict__ seq_dense) {
+                uint32_t *__restrict__ row_tax, const uint32_t *__restrict__ seq_dense, uint32_t rt_shift) {
   // text / tpos5 (both or neither) and row_tax are optional: the walk fills what the index had room for
-  const uint64_t tvm = (1ull << tv_shift) - 1ull;
+  // (rt_shift: row_tax is the table of every 2^rt_shift-th row, DevIndex::row_tax_s; 0 = of every row)
+  const uint64_t tvm = (1ull << tv_shift) - 1ull, rtm = (1ull << rt_shift) - 1ull;
   uint64_t k = 0, g = 0, left = 0;
   uint32_t dq = 0xffffffffu;
   bool active = false;
@@ -965,7 +977,7 @@ k_seq_walk_fill(DevIndex ix, uint32_t *next, const uint32_t *__restrict__ t_seq,
       k = t; g = off[(size_t)q + 1]; left = (uint64_t)len[q] + 1; active = true;
       if (row_tax) dq = seq_dense[q];
     }
-    if (row_tax) row_tax[k] = dq;
+    if (row_tax && (k & rtm) == 0) row_tax[k >> rt_shift] = dq;
     const uint32_t c = symbol_at(ix, k);
     if (text) {
       if ((k & tvm) == 0) put_tpos5(tpos5, k >> tv_shift, g);
@@ -1425,6 +1437,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
   //      two streams allocate later (scratch of the search lanes, peptides, fragment lists: up to ~4 GB for 10 M-read batches) -
   //      an index that does not leave that much goes without the text arrays rather than failing in kaiju_gpu_create ----
   d.sa_full = nullptr; d.text = nullptr; d.row_tax = nullptr; d.tax_of_dense = nullptr; d.n_dense = 0;
+  d.row_tax_s = nullptr; d.rts_shift = 0;
   d.beyond_lo = d.beyond_n = d.beyond_row = 0;
   uint64_t text_bytes = 0;
   {
@@ -1528,7 +1541,10 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
   //      28 G rows with every protein seven times: 25 of 64 ms).  It comes FIRST when HBM is short (the text arrays save 6 % of
   //      the search kernel, section 5b of DESIGN.md): built when it fits - with 8 GB for the classification contexts - in 70 % of
   //      the free HBM, i.e. up to about 30 G rows on a 288 GB MI355X (112 GB at 28 G rows next to the index's 92 GB);
-  //      KAIJU_GPU_ROW_TAX=0 / 1 overrides.  Filled by the same walk of every sequence that writes the text ----
+  //      KAIJU_GPU_ROW_TAX=0 / 1 overrides.  Filled by the same walk of every sequence that writes the text.
+  //      An index too big for it (a refseq-class one: 56 - 60 G rows) gets the table of every 2^s-th row, s = 1 .. 3 and below
+  //      the exponent of the suffix array's sample (DevIndex::row_tax_s: 60 GB at 60 G rows and s = 2) - the smallest s that
+  //      fits by the same rule, or KAIJU_GPU_ROW_TAX_SHIFT=s; the decision is plan_row_tax's (kj_rowtax_plan.h) ----
   // (not on an index with the reference's short sample array: a text-grown match is recorded through the row where the text took
   //  over, the lanes without the arrays record its own end row - and whether that row lies behind the missing sample would then
   //  depend on whether the arrays fit; the narrow lane applies the skip to the grown match itself, DevIndex::beyond_lo.  The
@@ -1538,10 +1554,13 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     const uint64_t tb_est = pk.bwtlen + 3 * (uint64_t)kTextPad, tmp = (uint64_t)pk.nseq * 20 + 64;
-    const uint64_t rt_est = pk.bwtlen * 4 + 64;
-    bool rt = (double)(rt_est + tmp + (8ull << 30)) <= 0.7 * (double)free_b;
-    if (const char *e = getenv("KAIJU_GPU_ROW_TAX")) rt = atoi(e) != 0;
-    const double free_tv = (double)free_b - (rt ? (double)rt_est : 0.0);
+    const RowTaxPlan rtp = plan_row_tax(pk.bwtlen, pk.nseq, pk.chpt_exp, free_b, getenv("KAIJU_GPU_ROW_TAX"), getenv("KAIJU_GPU_ROW_TAX_SHIFT"));
+    if (rtp.shift_ignored)
+      fprintf(stderr, "[kaiju_gpu load] KAIJU_GPU_ROW_TAX_SHIFT=%s ignored: the shift must be 0 .. %u and below the exponent of the suffix array's sample (%u)\n",
+              getenv("KAIJU_GPU_ROW_TAX_SHIFT"), kRowTaxMaxShift, pk.chpt_exp);
+    bool rt = rtp.kind != RowTaxPlan::None;
+    const uint32_t rt_shift = rtp.shift;
+    const double free_tv = (double)free_b - (double)rtp.bytes;      // (the bytes planned: the whole table or the sampled one)
     int tv = -1;
     if (const char *e = getenv("KAIJU_GPU_TV_SHIFT")) { const int v = atoi(e); if (v >= 0 && v <= 8) tv = v; }
     else if (pk.bwtlen < (1ull << 34))
@@ -1586,7 +1605,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
           std::vector<uint32_t> seq_dense;
           std::vector<uint64_t> tax_of_dense;
           dense_taxa(pk.seq_taxid, pk.seq_valid, seq_dense, tax_of_dense);
-          rowtax_bytes = pk.bwtlen * 4 + 64;                   // (+ slack: the many-rows locate reads 16 bytes at a time)
+          rowtax_bytes = rtp.bytes;                            // (+ slack: the many-rows locate reads 16 bytes at a time)
           if (upload(ix.get(), seq_dense, &d_sd) == 0) { ix->allocs.pop_back(); } else d_sd = nullptr;
           if (d_sd && upload(ix.get(), tax_of_dense, &d_td) == 0) { ix->allocs.pop_back(); } else d_td = nullptr;
           if (!(d_sd && d_td && hipMalloc((void **)&row_tax, rowtax_bytes) == hipSuccess)) {
@@ -1598,7 +1617,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
           if (text) { (void)hipMemset(text, 0, text_bytes); (void)hipMemset(tpos, 0xff, tpos_bytes - 16); (void)hipMemset(tpos + tpos_bytes - 16, 0, 16); }   // (all ones: no entry; the pad is zero)
           if (row_tax) (void)hipMemset(row_tax, 0xff, rowtax_bytes);
           (void)hipMemset(d_cnt, 0, 16);
-          hipLaunchKernelGGL(k_seq_walk_fill, dim3(blocks), dim3(256), 0, 0, d, d_cnt, t_seq, d_len, d_off, text, tpos, (uint32_t)std::max(tv, 0), row_tax, d_sd);
+          hipLaunchKernelGGL(k_seq_walk_fill, dim3(blocks), dim3(256), 0, 0, d, d_cnt, t_seq, d_len, d_off, text, tpos, (uint32_t)std::max(tv, 0), row_tax, d_sd, rt_shift);
           ok = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
         }
       }
@@ -1606,7 +1625,10 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
       for (void *q : {(void *)t_seq, (void *)d_len, (void *)d_off, (void *)d_cnt, (void *)d_sd}) if (q) (void)hipFree(q);
       if (ok && text) { ix->allocs.push_back(text); ix->allocs.push_back(tpos); d.text = text; d.sa_tpos5 = tpos; d.tv_shift = (uint32_t)tv; }
       else { if (text) (void)hipFree(text); if (tpos) (void)hipFree(tpos); text_bytes = 0; tpos_bytes = 0; }
-      if (ok && row_tax) { ix->allocs.push_back(row_tax); ix->allocs.push_back(const_cast<uint64_t *>(d_td)); d.row_tax = row_tax; d.tax_of_dense = d_td; }
+      if (ok && row_tax) {
+        ix->allocs.push_back(row_tax); ix->allocs.push_back(const_cast<uint64_t *>(d_td)); d.tax_of_dense = d_td;
+        if (rt_shift) { d.row_tax_s = row_tax; d.rts_shift = rt_shift; } else d.row_tax = row_tax;
+      }
       else { if (row_tax) (void)hipFree(row_tax); if (d_td) (void)hipFree(const_cast<uint64_t *>(d_td)); rowtax_bytes = 0; d.n_dense = 0; }
     }
     lc.mark("text + text positions, row -> taxon table (device, 64-bit rows)");
@@ -1634,7 +1656,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
     f.other = sizeof(ConstTables) + sizeof(Stage1Tables) + lnfact.size() * 8;
     f.text = d.text ? text_bytes : 0;
     ix->tpos_bytes = d.sa_tpos5 ? tpos_bytes : 0;
-    f.sa_full = d.sa_full ? pk.bwtlen * 8 : (d.sa_tpos5 ? tpos_bytes : 0) + (d.mb_base && d.row_tax ? rowtax_bytes : 0);   // (+ the taxon of every row, DevIndex::row_tax; wide: the text positions + that table)
+    f.sa_full = d.sa_full ? pk.bwtlen * 8 : (d.sa_tpos5 ? tpos_bytes : 0) + (d.mb_base && (d.row_tax || d.row_tax_s) ? rowtax_bytes : 0);   // (+ the taxon of every row, DevIndex::row_tax; wide: the text positions + that table, or the sampled one: row_tax_s)
     f.total = f.rank_blocks + f.count_bases + f.sa_seq + f.sa_taxid + f.seq_tables + f.kmer_table + f.kmer_lines + f.other + f.text + f.sa_full;
     f.kmer_k = std::max(d.kmer_k, d.kline_k); f.wide = d.mb_base ? 1u : 0u;
     inf.device_bytes = f.total;
@@ -1908,6 +1930,7 @@ extern "C" int kaiju_gpu_index_get_layout(const kaiju_gpu_index *ix, kaiju_gpu_i
   out->bwtlen = d.bwtlen; out->n_sa = d.n_sa; out->sa_skip = d.sa_skip; out->nseq = d.nseq; out->chpt_exp = d.chpt_exp;
   out->mb_shift = d.mb_shift; out->kmer_k = d.kmer_k; out->kline_k = d.kline_k; out->tv_shift = d.tv_shift; out->n_dense = d.n_dense;
   out->beyond_lo = d.beyond_lo; out->beyond_n = d.beyond_n; out->beyond_row = d.beyond_row; out->wide = d.mb_base ? 1u : 0u;
+  out->row_tax_shift = d.row_tax_s ? d.rts_shift : 0u;
   return KAIJU_GPU_OK;
   });
 }
@@ -2263,6 +2286,7 @@ static void launch_locate(const kaiju_gpu_ctx *c, hipStream_t s, FlowLocate how,
       break;
     case FlowLocate::Team: hipLaunchKernelGGL(k_mem_locate_team, grid_team, dim3(256), 0, s, ix->dev, p, b); break;
     case FlowLocate::WideWalk: hipLaunchKernelGGL(k_mem_locate_wide, grid_team, dim3(256), 0, s, ix->dev, p, b); break;
+    case FlowLocate::SampledWide: hipLaunchKernelGGL(k_mem_locate_sampled, grid_team, dim3(256), 0, s, ix->dev, p, b); break;
     case FlowLocate::InLane: case FlowLocate::Fused: break;
   }
 }
@@ -3684,6 +3708,64 @@ extern "C" int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const
     }
   }
   *n_frags = nf; *n_lr = nl;
+  return KAIJU_GPU_OK;
+  });
+}
+
+// Diagnostics (include/kaiju_gpu.h): the locate kernels of this context's plan over records that hold the given intervals as
+// pending matches - what the second-generation lanes leave behind (kHitLocPending) - on the buffers launch_batch uses.  Blocking.
+static_assert(KAIJU_GPU_LOCATE_MAX_INTERVALS <= (int)kLocMaxEntries && KAIJU_GPU_LOCATE_MAX_INTERVALS <= kMaxIds, "a record holds the intervals");
+extern "C" int kaiju_gpu_locate_intervals(kaiju_gpu_ctx *ctx, const uint64_t *lo, const uint32_t *len, const uint32_t *first,
+                                          uint32_t n_records, kaiju_gpu_hit *out) {
+  return guarded([&]() -> int {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  if (n_records > KAIJU_GPU_LOCATE_MAX_RECORDS) return fail(KAIJU_GPU_ERR_ARG, "more than KAIJU_GPU_LOCATE_MAX_RECORDS records in one call");
+  if (!ctx || !first || (!out && n_records)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (n_records == 0) return KAIJU_GPU_OK;
+  kaiju_gpu_ctx *c = ctx;
+  const kaiju_gpu_index *ix = c->ix;
+  const DevIndex &d = ix->dev;
+  const uint32_t n = n_records;
+  if (first[0] != 0) return fail(KAIJU_GPU_ERR_ARG, "first[0] must be 0");
+  if (first[n] && (!lo || !len)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  const bool wide = d.mb_base != nullptr;
+  std::vector<Hit> recs(n);
+  memset(recs.data(), 0, (size_t)n * sizeof(Hit));
+  for (uint32_t r = 0; r < n; r++) {
+    if (first[r + 1] < first[r]) return fail(KAIJU_GPU_ERR_ARG, "first[] must be non-decreasing");
+    const uint32_t k = first[r + 1] - first[r];
+    if (k > KAIJU_GPU_LOCATE_MAX_INTERVALS) return fail(KAIJU_GPU_ERR_ARG, "a record holds at most 16 intervals");
+    for (uint32_t q = 0; q < k; q++) {
+      const uint64_t l0 = lo[first[r] + q], ln = len[first[r] + q];
+      if (ln == 0 || l0 >= d.bwtlen || ln > d.bwtlen - l0) return fail(KAIJU_GPU_ERR_ARG, "an interval leaves the index");
+      if (wide ? ln >= kLocWideMaxLen : ln > 0x7fffffffull) return fail(KAIJU_GPU_ERR_ARG, "an interval is longer than a record can note");
+      recs[r].taxid[q] = wide ? (l0 | ln << kLocWideShift) : (l0 | ln << 32);
+    }
+    recs[r].n_ids = k;
+    recs[r].flags = kHitLocPending;
+  }
+  // the locate of a classification call of this context (kj_flow.h); the fused post-search pass locates with k_mem_locate's walk
+  const FlowPlan plan = plan_call(c, 0, n, 0, 0, false);
+  int rc;
+  if ((rc = plan_status(plan))) return rc;
+  const FlowLocate how = plan.locate == FlowLocate::Fused ? FlowLocate::RowTax : plan.locate;
+  if (how == FlowLocate::InLane)
+    return fail(KAIJU_GPU_ERR_UNSUPPORTED, "this context's search lanes locate their matches themselves: there is no locate kernel to run");
+  KJ_HIP(hipSetDevice(ix->device));
+  if ((rc = ensure(c->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
+  if ((rc = ensure(c->counters, 4096))) return rc;
+  if ((rc = ensure(c->loc_list, (size_t)n * 4 + 16))) return rc;
+  hipStream_t s = c->stream;
+  uint32_t *cnt = static_cast<uint32_t *>(c->counters.p);
+  KJ_HIP(hipMemsetAsync(cnt, 0, kCntProf * sizeof(uint32_t), s));
+  KJ_HIP(hipMemcpyAsync(c->h_hits.p, recs.data(), (size_t)n * sizeof(Hit), hipMemcpyHostToDevice, s));
+  Batch b{};
+  b.n_reads = n; b.hits = static_cast<Hit *>(c->h_hits.p);
+  launch_locate(c, s, how, c->kp, b, static_cast<uint32_t *>(c->loc_list.p), cnt + (c->kp.mode == 0 ? kCntLocListMem : kCntLocListGreedy));
+  KJ_HIP(hipGetLastError());
+  KJ_HIP(hipMemcpyAsync(out, c->h_hits.p, (size_t)n * sizeof(kaiju_gpu_hit), hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
   return KAIJU_GPU_OK;
   });
 }

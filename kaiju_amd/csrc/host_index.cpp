@@ -1,5 +1,6 @@
 // host_index.cpp — see host_index.h
 #include "host_index.h"
+#include "kj_rowtax_plan.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -626,7 +627,7 @@ int PackedIndex::read_image(const char *path, std::string &msg, bool lazy_big) {
 // of their terminator suffixes, sequence s (in the numbering of the samples) at text[off[s]] = 0, text[off[s] + 1 ..] = residues.
 void PackedIndex::build_text_wide(uint32_t shift) {
   sa_full.clear(); text.clear(); row_seq.clear(); sa_tpos5.clear();
-  tv_shift = shift;
+  tv_shift = shift; rts_shift = 0;
   if (!wide || blocks64.empty() || term_pos.empty() || shift > 8 || (warnings & KAIJU_IDX_WARN_SA_SHORT)) return;   // (as capi.hip decides)
   const DevIndex d = host_view();
   std::vector<uint32_t> t_seq(nseq), len(nseq, 0);
@@ -649,25 +650,34 @@ void PackedIndex::build_text_wide(uint32_t shift) {
   text.assign((size_t)(off[nseq] + 2 * kTextPad), 0);
   sa_tpos5.assign((size_t)(((bwtlen >> shift) + 1) * 5 + 16), 0xff);
   for (size_t x = sa_tpos5.size() - 16; x < sa_tpos5.size(); x++) sa_tpos5[x] = 0;      // (all ones: no entry; the pad is zero)
-  // the row -> dense taxon index table of a wide index (capi.hip builds it where HBM has room; KAIJU_EMU_NO_ROW_TAX: without)
+  // the row -> dense taxon index table of a wide index (capi.hip builds it where HBM has room; KAIJU_EMU_NO_ROW_TAX: without;
+  // KAIJU_EMU_ROW_TAX_SHIFT=s: the table of every 2^s-th row, s = 1 .. 3 and below the sample's exponent as plan_row_tax wants it)
   std::vector<uint32_t> seq_dense;
   const bool rt = !getenv("KAIJU_EMU_NO_ROW_TAX");
+  uint32_t rts = 0;
+  if (const char *e = getenv("KAIJU_EMU_ROW_TAX_SHIFT")) {
+    const RowTaxPlan rp = plan_row_tax(bwtlen, nseq, chpt_exp, ~0ull, nullptr, e);
+    if (rp.shift_ignored) fprintf(stderr, "[kaiju emu] KAIJU_EMU_ROW_TAX_SHIFT=%s ignored\n", e);
+    rts = rp.shift;
+  }
   if (rt) {
     dense_taxa(seq_taxid, seq_valid, seq_dense, tax_of_dense);
-    row_seq.resize((size_t)bwtlen + 16);
+    rts_shift = rts;
+    row_seq.resize(rts ? (size_t)(bwtlen >> rts) + 1 + 16 : (size_t)bwtlen + 16);
     for (size_t r = 0; r < row_seq.size(); r++) row_seq[r] = 0xffffffffu;
   }
   parallel_for(((uint64_t)nseq + 255) / 256, [&](uint64_t chunk) {
     const uint64_t b = chunk * 256, e = std::min<uint64_t>(nseq, b + 256);
     for (uint64_t t = b; t < e; t++) {
       const uint32_t q = t_seq[(size_t)t];
-      seq_walk_fill(d, t, off[(size_t)q + 1], len[q], text.data(), sa_tpos5.data(), shift, rt ? row_seq.data() : nullptr, rt ? seq_dense[q] : 0xffffffffu);
+      seq_walk_fill(d, t, off[(size_t)q + 1], len[q], text.data(), sa_tpos5.data(), shift, rt ? row_seq.data() : nullptr, rt ? seq_dense[q] : 0xffffffffu, rts);
     }
   });
 }
 
 void PackedIndex::build_text() {
   sa_full.clear(); text.clear(); row_seq.clear(); sa_tpos5.clear();
+  rts_shift = 0;
   if (wide || sa_pos.empty() || blocks64.empty() || bwtlen + nseq + 2 * kTextPad >= 0xffffffffull) return;
   const DevIndex d = host_view();
   BigVec<uint32_t> rs((size_t)bwtlen + 4), rp((size_t)bwtlen);      // (rs: four entries of padding for the locate's 16-byte loads)
@@ -754,7 +764,8 @@ DevIndex PackedIndex::host_view() const {
   d.kline = kline.empty() ? nullptr : kline.data(); d.kline_k = kline.empty() ? 0u : kmer_k;
   d.sa_full = sa_full.empty() ? nullptr : sa_full.data();
   d.text = text.empty() ? nullptr : text.data();
-  d.row_tax = row_seq.empty() ? nullptr : row_seq.data();
+  d.row_tax = row_seq.empty() || rts_shift ? nullptr : row_seq.data();
+  d.row_tax_s = row_seq.empty() || !rts_shift ? nullptr : row_seq.data(); d.rts_shift = d.row_tax_s ? rts_shift : 0u;
   d.tax_of_dense = tax_of_dense.empty() ? nullptr : tax_of_dense.data(); d.n_dense = (uint32_t)tax_of_dense.size();
   d.beyond_lo = beyond_lo; d.beyond_n = getenv("KAIJU_EMU_NO_BEYOND_RULE") ? 0u : beyond_n; d.beyond_row = beyond_row;   // (the knob: tests show what the rule is for)
   d.sa_tpos5 = sa_tpos5.empty() ? nullptr : sa_tpos5.data(); d.tv_shift = tv_shift;

@@ -95,6 +95,7 @@ struct PackedIndex {
   // text verification (DevIndex::sa_full / text), built on the HOST for the test emulation only - the device builds its own
   BigVec<uint32_t> sa_full, row_seq;    // (row_seq: DevIndex::row_tax once build_text is through - dense taxon indices)
   std::vector<uint64_t> tax_of_dense;
+  uint32_t rts_shift = 0;           // > 0: row_seq is the SAMPLED table of a wide index (DevIndex::row_tax_s / rts_shift)
   uint32_t beyond_lo = 0, beyond_n = 0, beyond_row = 0;   // DevIndex::beyond_*
   BigVec<uint8_t> text;
   BigVec<uint8_t> sa_tpos5;       // wide layout: DevIndex::sa_tpos5 (text position of every 2^tv_shift-th row)

@@ -124,6 +124,13 @@ struct DevIndex {
   // step on average), then compares with the text as the narrow lane does.
   const uint8_t *sa_tpos5;   // [(bwtlen >> tv_shift) + 1] entries of 5 bytes (little endian), 16 bytes of padding behind; nullptr = none
   uint32_t tv_shift;
+  // the row -> taxon table SAMPLED (wide indexes too big for row_tax, e.g. 60 G rows: 60 GB at rts_shift = 2 where the full table
+  // would be 241 GB): entry i = what row_tax would hold for row i << rts_shift.  The locate walks from a row as it does towards
+  // the sample of the suffix array, and ends at the first row that is a multiple of 2^rts_shift (or at a terminator): about
+  // 2^rts_shift LF steps on average where the walk to sa_iseq takes about 2^chpt_exp, and never more than that walk
+  // (k_mem_locate_sampled).  An index has row_tax, row_tax_s or neither; tax_of_dense / n_dense serve both.
+  const uint32_t *row_tax_s = nullptr;   // [(bwtlen >> rts_shift) + 1] (+ 64 bytes of slack); nullptr = none
+  uint32_t rts_shift = 0;                // 1 .. 3 and < chpt_exp where row_tax_s is set, 0 otherwise
 };
 constexpr uint64_t kTposNone = (1ull << 40) - 1ull;
 constexpr uint32_t kBeyondRowsMax = 4096;    // rows whose walk passes the missing sample of a KAIJU_IDX_WARN_SA_SHORT index (a few)
@@ -261,7 +268,7 @@ inline void index_arrays(const DevIndex &d, uint64_t text_bytes, uint64_t tpos_b
       {d.kline, d.kline ? nlw * kKLineBytes : 0},
       {d.text, d.text ? text_bytes : 0},
       {d.sa_full ? (const void *)d.sa_full : (const void *)d.sa_tpos5, d.sa_full ? d.bwtlen * 4 : d.sa_tpos5 ? tpos_bytes : 0},
-      {d.row_tax, d.row_tax ? d.bwtlen * 4 : 0},
+      {d.row_tax ? d.row_tax : d.row_tax_s, d.row_tax ? d.bwtlen * 4 : d.row_tax_s ? ((d.bwtlen >> d.rts_shift) + 1) * 4 + 64 : 0},
       {d.tax_of_dense, d.tax_of_dense ? (uint64_t)d.n_dense * 8 : 0}};
   for (int x = 0; x < kIndexArrays; x++) { out[x] = a[x]; if (!out[x].p || !out[x].bytes) out[x] = IndexArr{nullptr, 0}; }
 }
@@ -547,14 +554,15 @@ KJ_HD void put_tpos5(uint8_t *a, uint64_t idx, uint64_t g) {
   e[0] = (uint8_t)g; e[1] = (uint8_t)(g >> 8); e[2] = (uint8_t)(g >> 16); e[3] = (uint8_t)(g >> 24); e[4] = (uint8_t)(g >> 32);
 }
 // row_tax (optional): every row on the way also gets `dense`, the dense taxon index of the walk's sequence (DevIndex::row_tax
-// of an index with 64-bit positions; text / tpos5 may then be null)
+// of an index with 64-bit positions; text / tpos5 may then be null) - every 2^rt_shift-th row into entry k >> rt_shift for the
+// sampled table (DevIndex::row_tax_s)
 KJ_HD void seq_walk_fill(const DevIndex &ix, uint64_t t, uint64_t g_end, uint64_t n, uint8_t *text, uint8_t *tpos5, uint32_t tv_shift,
-                         uint32_t *row_tax = nullptr, uint32_t dense = 0xffffffffu) {
-  const uint64_t tvm = (1ull << tv_shift) - 1ull;
+                         uint32_t *row_tax = nullptr, uint32_t dense = 0xffffffffu, uint32_t rt_shift = 0) {
+  const uint64_t tvm = (1ull << tv_shift) - 1ull, rtm = (1ull << rt_shift) - 1ull;
   uint64_t k = t, g = g_end;
   for (uint64_t step = 0; step <= n; step++) {
     if (tpos5 && (k & tvm) == 0) put_tpos5(tpos5, k >> tv_shift, g);
-    if (row_tax) row_tax[k] = dense;
+    if (row_tax && (k & rtm) == 0) row_tax[k >> rt_shift] = dense;   // (rt_shift: the sampled table, DevIndex::row_tax_s)
     const uint32_t c = symbol_at(ix, k);
     if (text) text[g - 1] = (uint8_t)c;
     if (c == 0) return;
@@ -3474,6 +3482,8 @@ KJ_HD void mem_verbose_read(const DevIndex &ix, const Params &p, const Batch &b,
 // matches hold seven rows costs seven walks one after the other: 18.5 ms per 5 M pairs on a 28 G-row index with every protein
 // seven times (profiles/r04_refseq_ref), a third of the step.  Team: how a lane learns what its team mates found -
 //   TeamWave<T> (device): shuffles;  TeamSerial<T> (host emulation): the T walks run one after the other into an array.
+// A Team also has lf_step(), called once per LF step of a walk: TeamSerial counts them (the tests of the sampled row -> taxon
+// table hold every walk's length to the index's own LF), TeamWave's is empty and leaves no instruction in the kernels.
 template <int T>
 struct TeamSerial {
   uint64_t vals[T], vals2[T];
@@ -3484,6 +3494,8 @@ struct TeamSerial {
   KJ_HD uint64_t get2(int q) const { return vals2[q]; }
   KJ_HD bool leader() const { return true; }
   KJ_HD bool from_leader(bool v) const { return v; }
+  uint64_t lf_steps = 0;                   // LF steps the walks of this team have taken (tests: what a walk to a 2^s-th row costs)
+  KJ_HD void lf_step() { lf_steps++; }
   // the matches of the read (row | length, up to kLocMaxEntries), copied before the first id is written over them
   uint64_t ent[kLocMaxEntries];
   KJ_HD void load_entries(const uint64_t *rec, uint32_t n) { for (uint32_t q = 0; q < kLocMaxEntries; q++) ent[q] = q < n ? rec[q] : 0ull; }
@@ -3504,6 +3516,7 @@ struct TeamWave {
     return (uint64_t)(uint32_t)__shfl((int)(uint32_t)mine2, src, 64) | (uint64_t)(uint32_t)__shfl((int)(uint32_t)(mine2 >> 32), src, 64) << 32;
   }
   __device__ __forceinline__ bool leader() const { return (threadIdx.x & (T - 1)) == 0; }
+  __device__ __forceinline__ void lf_step() const {}             // (counted by the host emulation only)
   __device__ __forceinline__ bool from_leader(bool v) const { return __shfl((int)v, (int)((threadIdx.x & 63u) & ~(uint32_t)(T - 1)), 64) != 0; }
   // the matches of the read (row | length, up to kLocMaxEntries): lane t of the team keeps entries t, t + T, .. in registers - the
   // leader writes ids over them later - and hands one out by a shuffle
@@ -3524,15 +3537,21 @@ struct TeamWave {
 #ifndef KJ_LOC_ILP
 #define KJ_LOC_ILP 1                      // rows a lane of a locate team walks side by side (2: DESIGN.md 6b, round 6)
 #endif
-template <bool WIDE, int T, class Team>
+// SAMPLED (wide indexes with DevIndex::row_tax_s, k_mem_locate_sampled): the walk of a row ends at the first row that is a multiple
+// of 2^rts_shift - one load of the sampled row -> taxon table, then tax_of_dense - or at a terminator letter as before.  Every row
+// the walk to the suffix array's sample passes is passed by this one too until it ends (rts_shift < chpt_exp: a sampled row of
+// the suffix array is one of this table), so it never takes more LF steps, and never reads sa_iseq.  A template parameter, not a
+// branch in the walk: the two other instantiations stay what they were.
+template <bool WIDE, int T, bool SAMPLED = false, class Team>
 KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, Team &team) {
+  static_assert(!SAMPLED || WIDE, "the sampled row -> taxon table is for indexes with 64-bit positions");
   typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type P;
   const uint32_t fl0 = hit->flags;                            // (every lane of the team reads the same record: team-uniform)
   if (!(fl0 & kHitLocPending)) return;
   const uint32_t nsi = hit->n_ids;
   // the matches (row | length): every lane of the team keeps its share before the leader writes the first id
   team.load_entries(hit->taxid, nsi);
-  const P check = (P)((1ull << ix.chpt_exp) - 1ull);
+  const P check = SAMPLED ? (P)((1ull << ix.rts_shift) - 1ull) : (P)((1ull << ix.chpt_exp) - 1ull);
   const RankBlock64 *const blk0 = ix.blocks64;
   uint32_t nids = 0, flags = fl0 & ~kHitLocPending;           // (the leader's; a Greedy read may carry kHitSiCap already)
   uint64_t id0 = 0;
@@ -3544,12 +3563,18 @@ KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, T
   };
   // the id of one row: ~0 = none (a name without a usable id, or a row beyond the samples, where the reference reads out of bounds)
   auto walk = [&](P k) -> uint64_t {
-    if (ix.row_tax) {                                         // the walk below, precomputed for every row at index load (k_suffix_walk)
-      const uint32_t t = ix.row_tax[k];
-      return t != 0xffffffffu ? ix.tax_of_dense[t] : ~0ull;
+    if constexpr (!SAMPLED) {
+      if (ix.row_tax) {                                       // the walk below, precomputed for every row at index load (k_suffix_walk)
+        const uint32_t t = ix.row_tax[k];
+        return t != 0xffffffffu ? ix.tax_of_dense[t] : ~0ull;
+      }
     }
     for (;;) {
       if ((k & check) == 0) {
+        if constexpr (SAMPLED) {                              // a row of the sampled table: its taxon, as row_tax would give it
+          const uint32_t t = ix.row_tax_s[(uint64_t)k >> ix.rts_shift];
+          return t != 0xffffffffu ? ix.tax_of_dense[t] : ~0ull;
+        }
         const uint64_t sa_idx = ((uint64_t)k >> ix.chpt_exp) - ix.sa_skip;
         if (sa_idx >= ix.n_sa) return ~0ull;
         if constexpr (WIDE) { const uint32_t iseq = ix.sa_iseq[sa_idx]; return iseq < ix.nseq ? ix.seq_taxid[iseq] : ~0ull; }
@@ -3571,6 +3596,7 @@ KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, T
       uint64_t base = 0;
       if constexpr (WIDE) base = ix.mb_base[(size_t)((uint64_t)k >> ix.mb_shift) * 20 + (c - 1u)];
       k = (P)(base + rb.cnt[c - 1u] + popc64(m & ((1ull << sft) - 1ull)));
+      team.lf_step();
     }
   };
   bool done = false;                                          // team-uniform
@@ -3588,7 +3614,9 @@ KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, T
     for (P row0 = lo; row0 < rowend && !done; row0 += (P)(2 * T)) {
       team.compute2([&](int tl, uint64_t &ta, uint64_t &tb) {
         const P ra = row0 + (P)tl, rb2 = row0 + (P)T + (P)tl;
-        if (ix.row_tax) { ta = ra < rowend ? walk(ra) : ~0ull; tb = rb2 < rowend ? walk(rb2) : ~0ull; return; }
+        if constexpr (!SAMPLED) {
+          if (ix.row_tax) { ta = ra < rowend ? walk(ra) : ~0ull; tb = rb2 < rowend ? walk(rb2) : ~0ull; return; }
+        }
         P k[2] = {ra, rb2};
         bool fin[2] = {!(ra < rowend), !(rb2 < rowend)};
         uint64_t res[2] = {~0ull, ~0ull};
@@ -3598,7 +3626,11 @@ KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, T
 #pragma unroll
           for (int h = 0; h < 2; h++) {
             if (!fin[h] && (k[h] & check) == 0) {
-              const uint64_t sa_idx = ((uint64_t)k[h] >> ix.chpt_exp) - ix.sa_skip;
+              const uint64_t sa_idx = SAMPLED ? 0ull : ((uint64_t)k[h] >> ix.chpt_exp) - ix.sa_skip;
+              if constexpr (SAMPLED) {                        // (the sampled row -> taxon table: see walk)
+                const uint32_t t = ix.row_tax_s[(uint64_t)k[h] >> ix.rts_shift];
+                if (t != 0xffffffffu) res[h] = ix.tax_of_dense[t];
+              } else
               if (sa_idx < ix.n_sa) {
                 if constexpr (WIDE) { const uint32_t iseq = ix.sa_iseq[sa_idx]; res[h] = iseq < ix.nseq ? ix.seq_taxid[iseq] : ~0ull; }
                 else res[h] = ix.sa_taxid[sa_idx];
@@ -3642,6 +3674,7 @@ KJ_HD void mem_locate_read_team(const DevIndex &ix, const Params &p, Hit *hit, T
                            id = (c & 8u) ? 0ull : ~0ull, ie = (c & 16u) ? 0ull : ~0ull;
             const uint64_t m = (pl[h][0] ^ ia) & (pl[h][1] ^ ib) & (pl[h][2] ^ ic) & (pl[h][3] ^ id) & (pl[h][4] ^ ie);
             k[h] = (P)(base[h] + cnt[h] + popc64(m & ((1ull << sft) - 1ull)));
+            team.lf_step();
           }
         }
         ta = res[0]; tb = res[1];

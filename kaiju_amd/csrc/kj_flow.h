@@ -21,10 +21,11 @@ struct FlowIndex {
   bool kmer64; uint32_t kmer_k;    // k-mer table with 64-bit positions
   bool wide;                       // mb_base: 64-bit positions
   bool row_tax;                    // the row -> taxon table
+  bool row_tax_sampled = false;    // ... of every 2^s-th row only (wide indexes, DevIndex::row_tax_s)
 };
 inline FlowIndex flow_index(const DevIndex &d) {
   return FlowIndex{d.blocks64 != nullptr, d.kline != nullptr, d.kline_k, d.kmer64 != nullptr, d.kmer_k, d.mb_base != nullptr,
-                   d.row_tax != nullptr};
+                   d.row_tax != nullptr, d.row_tax_s != nullptr};
 }
 
 // the parameters and the switches of a context
@@ -60,7 +61,7 @@ enum class FlowSeg : uint32_t { Off, Eager, Lazy };
 enum class FlowLane : uint32_t { MemV1, MemWideV1, Mem2, MemWide2, GreedyV1, Greedy2, Greedy2Wide, Greedy3 };
 enum class FlowInst : uint32_t { Plain, Counting, XOrder, Verbose };
 // who turns the matches the lanes found into ids
-enum class FlowLocate : uint32_t { InLane, RowTax, RowTaxWide, Team, WideWalk, Fused };
+enum class FlowLocate : uint32_t { InLane, RowTax, RowTaxWide, Team, WideWalk, Fused, SampledWide };
 
 struct FlowPlan {
   FlowStatus status = FlowStatus::Ok;
@@ -193,7 +194,7 @@ inline FlowPlan plan_flow(const FlowIndex &ix, const FlowSwitches &sw, const Flo
   if (!defer) f.locate = FlowLocate::InLane;
   else if (f.fused) f.locate = FlowLocate::Fused;
   else if (narrow) f.locate = ix.row_tax ? FlowLocate::RowTax : FlowLocate::Team;
-  else f.locate = ix.row_tax ? FlowLocate::RowTaxWide : FlowLocate::WideWalk;
+  else f.locate = ix.row_tax ? FlowLocate::RowTaxWide : ix.row_tax_sampled ? FlowLocate::SampledWide : FlowLocate::WideWalk;
   return f;
 }
 
