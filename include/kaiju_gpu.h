@@ -481,6 +481,67 @@ int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy
                                     char *out_text, uint64_t out_cap, kaiju_gpu_parse_info *info_parse,
                                     kaiju_gpu_format_info *info_format);
 
+/* ---- taxon names and lineages in the output lines: the column of kaiju-addTaxonNames ------------------------ */
+/* What kaiju-addTaxonNames (kaiju-addTaxonNames.cpp, util.cpp:123-192 of the reference) appends to the 'C' lines, written by
+   the passes that write the lines (kaiju_amd/csrc/format_names.hip; the rules: kj_format_names.h).  A 'C' line whose taxon is
+   no node of nodes.dmp as that tool parses it, or has no scientific name of its own, stays as it is; every other 'C' line
+   gets "\t" and the taxon's name (KAIJU_NAMES_NAME), its lineage root first, every name followed by "; " (KAIJU_NAMES_PATH, the
+   tool's -p), or the names at the ranks of a comma separated list, "NA" where the lineage has none (KAIJU_NAMES_RANKS, -r).
+   A tree with a cycle other than a node that is its own parent is refused (KAIJU_GPU_ERR_ARG; kaiju_gpu_last_error() names
+   a node on it), so is a list of more than KAIJU_NAMES_MAX_RANKS distinct ranks or KAIJU_NAMES_MAX_LIST items. */
+#define KAIJU_NAMES_NAME 0
+#define KAIJU_NAMES_PATH 1
+#define KAIJU_NAMES_RANKS 2
+#define KAIJU_NAMES_MAX_RANKS 16
+#define KAIJU_NAMES_MAX_LIST 64
+typedef struct kaiju_taxon_names kaiju_taxon_names;           /* host tables */
+typedef struct kaiju_gpu_taxon_names kaiju_gpu_taxon_names;   /* ... on a device, with the tables built there */
+/* Host only, no GPU.  ranks_csv: the list of KAIJU_NAMES_RANKS (NULL or ignored otherwise) */
+int kaiju_taxon_names_load(const char *nodes_dmp, const char *names_dmp, int mode, const char *ranks_csv, kaiju_taxon_names **out);
+void kaiju_taxon_names_free(kaiju_taxon_names *names);
+/* Host only, for inspection: the annotation of `taxon`, computed by walking the tree (not from the tables the device uses).
+   Returns its length - the first min(length, cap) bytes are in buf - or -1: the line stays unchanged */
+int64_t kaiju_taxon_names_annotation(const kaiju_taxon_names *names, uint64_t taxon, char *buf, uint64_t cap);
+/* nodes of the tree / nodes with a name of their own */
+uint64_t kaiju_taxon_names_count(const kaiju_taxon_names *names, int named);
+/* Upload, and the per-slot tables built by kernels there (lengths of the lineages; per rank the node that supplies it).
+   KAIJU_GPU_ERR_ARG when an annotation reaches 2^24 bytes */
+int kaiju_gpu_taxon_names_upload(const kaiju_taxon_names *names, int device_id, kaiju_gpu_taxon_names **out);
+void kaiju_gpu_taxon_names_free(kaiju_gpu_taxon_names *names);
+uint64_t kaiju_gpu_taxon_names_max_annotation(const kaiju_gpu_taxon_names *names);
+/* For inspection: the tables as they lie on the device, to the host.  which: 0 key (8 bytes per slot), 1 parent, 2 name_pos,
+   3 name_len, 4 path_len, 5 rank_len (4 each), 6 rank_src (4 * distinct ranks), 7 rank (1).  A table the mode does not build:
+   KAIJU_GPU_ERR_ARG.  *n_slots (may be NULL): slots of the table */
+int kaiju_gpu_taxon_names_read(const kaiju_gpu_taxon_names *names, int which, void *host_out, uint64_t out_bytes, uint64_t *n_slots);
+typedef struct kaiju_gpu_format_names_info {
+  uint64_t text_bytes;             /* the fields of kaiju_gpu_format_info, with the same meaning                            */
+  uint32_t n_records, n_classified;
+  uint32_t overflow;
+  uint32_t n_inexact;
+  uint32_t n_unknown_taxon;        /* 'C' lines left unchanged: the taxon is no node of the tree                           */
+  uint32_t n_unnamed_taxon;        /* 'C' lines left unchanged: the taxon has no name                                      */
+  uint32_t n_dropped;              /* 'U' lines left out (drop_unclassified)                                               */
+  uint32_t reserved;
+} kaiju_gpu_format_names_info;     /* 40 bytes */
+/* kaiju_gpu_format_compact_device / kaiju_gpu_format_compact with the column.  `names` must live on the context's device.
+   drop_unclassified: the tool's -u.  Lines are written whole or not at all, no byte at or behind out_cap is touched.
+   The scratch - 24 bytes per record - lives in the context. */
+int kaiju_gpu_format_names_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
+                                  const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names,
+                                  const kaiju_gpu_taxon_names *names, int drop_unclassified, void *d_out, uint64_t out_cap,
+                                  kaiju_gpu_format_names_info *d_info, void *stream);
+int kaiju_gpu_format_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, int paired,
+                           const char *text1, uint64_t bytes1, const kaiju_gpu_name_span *names_spans,
+                           const kaiju_gpu_taxon_names *names, int drop_unclassified, char *out, uint64_t out_cap,
+                           kaiju_gpu_format_names_info *info);
+/* Host only: an out_cap that cannot overflow: bytes1 + n * (25 + max_annotation) */
+uint64_t kaiju_gpu_format_names_bound(uint64_t bytes1, uint32_t n, const kaiju_gpu_taxon_names *names);
+/* kaiju_gpu_classify_text_to_text with the passes above at its end */
+int kaiju_gpu_classify_text_to_text_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
+                                          const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
+                                          const kaiju_gpu_taxon_names *names, int drop_unclassified, char *out_text, uint64_t out_cap,
+                                          kaiju_gpu_parse_info *info_parse, kaiju_gpu_format_names_info *info_format);
+
 /* ---- the lines of kaiju -v on the device: hits and matches in, text out ------------------------------------ */
 /* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi WITH -v, as HIP passes
    (kaiju_amd/csrc/format_verbose.hip; the rules: kj_format_verbose.h): the decision of the three-column lines, and for a

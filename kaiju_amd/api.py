@@ -76,6 +76,10 @@ NO_MISMATCH = 0xffffffff
 FORMAT_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"), ("n_classified", "<u4"), ("overflow", "<u4"),
                               ("n_inexact", "<u4")])                                           # kaiju_gpu_format_info
 assert NAME_SPAN_DTYPE.itemsize == 8 and PARSE_INFO_DTYPE.itemsize == 32 and FORMAT_INFO_DTYPE.itemsize == 24
+FORMAT_NAMES_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"), ("n_classified", "<u4"), ("overflow", "<u4"), ("n_inexact", "<u4"),
+                                    ("n_unknown_taxon", "<u4"), ("n_unnamed_taxon", "<u4"), ("n_dropped", "<u4"), ("reserved", "<u4")])
+assert FORMAT_NAMES_INFO_DTYPE.itemsize == 40
+NAMES_NAME, NAMES_PATH, NAMES_RANKS = 0, 1, 2
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -176,6 +180,26 @@ def lib():
                                            C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_classify_batch_seq_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]
+    if hasattr(L, "kaiju_taxon_names_load"):                  # (likewise)
+        L.kaiju_taxon_names_load.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p]
+        L.kaiju_taxon_names_free.argtypes = [C.c_void_p]
+        L.kaiju_taxon_names_annotation.restype = C.c_int64
+        L.kaiju_taxon_names_annotation.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        L.kaiju_taxon_names_count.restype = C.c_uint64
+        L.kaiju_taxon_names_count.argtypes = [C.c_void_p, C.c_int]
+        L.kaiju_gpu_taxon_names_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.kaiju_gpu_taxon_names_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_taxon_names_max_annotation.restype = C.c_uint64
+        L.kaiju_gpu_taxon_names_max_annotation.argtypes = [C.c_void_p]
+        L.kaiju_gpu_taxon_names_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_format_names_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_format_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_format_names_bound.restype = C.c_uint64
+        L.kaiju_gpu_format_names_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_void_p]
+        L.kaiju_gpu_classify_text_to_text_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                                            C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -357,6 +381,85 @@ class DeviceTaxonomy:
     def close(self):
         if self._h:
             lib().kaiju_gpu_taxonomy_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _names_mode(mode):
+    """'name', 'path', 'ranks:<list>' (or a pair (mode, list)) -> (mode, list)"""
+    if isinstance(mode, str):
+        if mode.startswith("ranks:"):
+            return NAMES_RANKS, mode[len("ranks:"):]
+        return {"name": NAMES_NAME, "path": NAMES_PATH}[mode], None
+    return mode
+
+
+class TaxonNames:
+    """nodes.dmp and names.dmp as kaiju-addTaxonNames reads them (kaiju_taxon_names_load; host only).  mode: "name", "path"
+    (the tool's -p) or "ranks:<comma separated list>" (-r)."""
+
+    def __init__(self, nodes_dmp: str, names_dmp: str, mode="name"):
+        if not hasattr(lib(), "kaiju_taxon_names_load"):
+            raise KaijuGpuError("this library was linked without taxon_names.cpp")
+        m, ranks = _names_mode(mode)
+        self.mode = m
+        self._h = C.c_void_p()
+        _check(lib().kaiju_taxon_names_load(nodes_dmp.encode(), names_dmp.encode(), m, ranks.encode() if ranks is not None else None, C.byref(self._h)))
+
+    def annotation(self, taxon: int):
+        """what the tool appends to a 'C' line of ``taxon`` (bytes), None: the line stays as it is"""
+        n = lib().kaiju_taxon_names_annotation(self._h, taxon, None, 0)
+        if n < 0:
+            return None
+        buf = np.zeros(n + 1, dtype=np.uint8)
+        assert lib().kaiju_taxon_names_annotation(self._h, taxon, buf.ctypes.data, n) == n
+        return buf[:n].tobytes()
+
+    def count(self, named=False):
+        return int(lib().kaiju_taxon_names_count(self._h, 1 if named else 0))
+
+    def close(self):
+        if self._h:
+            lib().kaiju_taxon_names_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceTaxonNames:
+    """TaxonNames in HBM, with the per-slot tables built there (kaiju_gpu_taxon_names_upload)."""
+    TABLES = {"key": (0, "<u8"), "parent": (1, "<u4"), "name_pos": (2, "<u4"), "name_len": (3, "<u4"), "path_len": (4, "<u4"), "rank_len": (5, "<u4"),
+              "rank_src": (6, "<u4"), "rank": (7, "u1")}
+
+    def __init__(self, names: TaxonNames, device: int = 0):
+        self._h = C.c_void_p()
+        _check(lib().kaiju_gpu_taxon_names_upload(names._h, device, C.byref(self._h)))
+
+    @property
+    def max_annotation(self):
+        return int(lib().kaiju_gpu_taxon_names_max_annotation(self._h))
+
+    def table(self, which: str, per_slot: int = 1):
+        """a table as it lies on the device (for inspection); per_slot: words per slot (rank_src: the distinct ranks)"""
+        k, dt = self.TABLES[which]
+        cap = C.c_uint64()
+        _check(lib().kaiju_gpu_taxon_names_read(self._h, k, None, 0, C.byref(cap)))
+        out = np.zeros(cap.value * per_slot, dtype=dt)
+        _check(lib().kaiju_gpu_taxon_names_read(self._h, k, out.ctypes.data, out.nbytes, None))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_taxon_names_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -611,6 +714,48 @@ class Classifier:
         _check(lib().kaiju_gpu_classify_text_to_text(self._h, dtax._h, t1.ctypes.data, len(t1) - 1, t2.ctypes.data if t2 is not None else None,
                                                      len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
                                                      out.ctypes.data, ocap, info.ctypes.data, finfo.ctypes.data))
+        return {"text": out[: int(finfo[0]["text_bytes"])].tobytes(), "info": info[0], "format_info": finfo[0]}
+
+    def format_names(self, recs: np.ndarray, off: np.ndarray, text1, names: np.ndarray, dnames: "DeviceTaxonNames", paired=False, drop_unclassified=False,
+                     out_cap=None, out=None):
+        """format_compact with the column of kaiju-addTaxonNames (kaiju_gpu_format_names).  Returns (out, info): info is a
+        FORMAT_NAMES_INFO_DTYPE record."""
+        recs = np.ascontiguousarray(recs, dtype=COMPACT_DTYPE)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=NAME_SPAN_DTYPE)
+        t1 = np.frombuffer(bytes(text1) + b"\0", dtype=np.uint8) if not isinstance(text1, np.ndarray) else np.concatenate([text1, np.zeros(1, dtype=np.uint8)])
+        n = len(recs)
+        assert len(off) == 2 * n + 1 and len(names) == n
+        cap = int(out_cap) if out_cap is not None else int(lib().kaiju_gpu_format_names_bound(len(t1) - 1, n, dnames._h))
+        if out is None:
+            out = np.zeros(cap + 1, dtype=np.uint8)
+        assert out.dtype == np.uint8 and len(out) >= cap
+        info = np.zeros(1, dtype=FORMAT_NAMES_INFO_DTYPE)
+        _check(lib().kaiju_gpu_format_names(self._h, recs.ctypes.data, off.ctypes.data, n, 1 if paired else 0, t1.ctypes.data, len(t1) - 1,
+                                            names.ctypes.data, dnames._h, 1 if drop_unclassified else 0, out.ctypes.data, cap, info.ctypes.data))
+        return out, info[0]
+
+    def format_names_device(self, d_recs_ptr: int, d_off_ptr: int, n: int, d_text1_ptr: int, bytes1: int, d_names_ptr: int, dnames: "DeviceTaxonNames",
+                            d_out_ptr: int, out_cap: int, d_info_ptr: int, paired=False, drop_unclassified=False, stream: int = 0):
+        """the same for device-resident buffers (raw pointers; d_out 16-byte aligned): kaiju_gpu_format_names_device,
+        asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_format_names_device(self._h, d_recs_ptr or None, d_off_ptr or None, n, 1 if paired else 0, d_text1_ptr or None, bytes1,
+                                                   d_names_ptr or None, dnames._h, 1 if drop_unclassified else 0, d_out_ptr or None, out_cap,
+                                                   d_info_ptr or None, stream or None))
+
+    def classify_text_to_text_names(self, dtax: "DeviceTaxonomy", dnames: "DeviceTaxonNames", text1, text2=None, fastq=True, keep_names=False,
+                                    drop_unclassified=False, rec_cap=None, out_cap=None):
+        """classify_text_to_text with the column of kaiju-addTaxonNames (kaiju_gpu_classify_text_to_text_names).  Returns a dict:
+        text (bytes), info (PARSE_INFO_DTYPE record), format_info (FORMAT_NAMES_INFO_DTYPE record)."""
+        t1, t2, cap = _text_args(text1, text2, rec_cap)
+        ocap = int(out_cap) if out_cap is not None else int(lib().kaiju_gpu_format_names_bound(len(t1) - 1, cap, dnames._h))
+        out = np.zeros(ocap + 1, dtype=np.uint8)
+        info = np.zeros(1, dtype=PARSE_INFO_DTYPE)
+        finfo = np.zeros(1, dtype=FORMAT_NAMES_INFO_DTYPE)
+        _check(lib().kaiju_gpu_classify_text_to_text_names(self._h, dtax._h, t1.ctypes.data, len(t1) - 1, t2.ctypes.data if t2 is not None else None,
+                                                           len(t2) - 1 if t2 is not None else 0, 1 if fastq else 0, 1 if keep_names else 0, cap,
+                                                           dnames._h, 1 if drop_unclassified else 0, out.ctypes.data, ocap, info.ctypes.data,
+                                                           finfo.ctypes.data))
         return {"text": out[: int(finfo[0]["text_bytes"])].tobytes(), "info": info[0], "format_info": finfo[0]}
 
     def format_verbose(self, hits: np.ndarray, v: np.ndarray, text_pos: np.ndarray, text, recs: np.ndarray, off: np.ndarray, names_text,

@@ -46,6 +46,7 @@
 #include "kj_format.h"
 #include "kj_format_verbose.h"
 #include "kj_format_seq.h"
+#include "kj_format_names.h"
 // Libraries linked from a source list of their own (the compile-time variants of tests/tools/mem_variants.sh: search lanes
 // only) need not hold ingest.hip: the two functions are weak references here, and without them the entry points below say
 // KAIJU_GPU_ERR_UNSUPPORTED.  kaiju_amd/build.py always links ingest.hip.
@@ -68,6 +69,12 @@ __attribute__((weak)) decltype(kj_fs_total) kj_fs_total;
 __attribute__((weak)) decltype(kj_fs_write) kj_fs_write;
 __attribute__((weak)) decltype(kj_fs_written) kj_fs_written;
 __attribute__((weak)) decltype(kj_fs_free) kj_fs_free;
+// (format_names.hip likewise)
+__attribute__((weak)) decltype(kj_fn_launch) kj_fn_launch;
+__attribute__((weak)) decltype(kj_fn_written) kj_fn_written;
+__attribute__((weak)) decltype(kj_fn_free) kj_fn_free;
+__attribute__((weak)) decltype(kj_fn_device) kj_fn_device;
+extern "C" __attribute__((weak)) decltype(kaiju_gpu_taxon_names_max_annotation) kaiju_gpu_taxon_names_max_annotation;
 #ifdef KJ_GREEDY3                    // the experimental row-pool Greedy lane: variant builds only
 #include "kj_greedy3.h"
 #endif
@@ -1043,6 +1050,8 @@ static int guarded(F &&f) {
 
 extern "C" int kaiju_gpu_abi_version(void) { return KAIJU_GPU_ABI_VERSION; }
 extern "C" const char *kaiju_gpu_last_error(void) { return tl_error.c_str(); }
+// (for the sources that keep no error text of their own: taxon_names.cpp, format_names.hip)
+extern "C" void kj_set_last_error(const char *msg) { tl_error = msg ? msg : ""; }
 extern "C" const char *kaiju_gpu_strerror(int status) {
   switch (status) {
     case KAIJU_GPU_OK: return "ok";
@@ -2020,6 +2029,7 @@ struct kaiju_gpu_ctx {
   kj_fv_scratch *format_v = nullptr;                   // the lines of -v (format_verbose.hip): lengths, offsets, the shadow
   DevBuf fv_out, fv_info, fv_trunc, fv_total;          // ... and the staging of its host-pointer entry points
   kj_fs_scratch *format_s = nullptr;                   // the lines of kaijux / kaijup (format_seq.hip); staged in fv_out / fv_info / fv_trunc
+  kj_fn_scratch *format_n = nullptr;                   // the lines with taxon names (format_names.hip); staged in fmt_out / fmt_info
   kaiju_gpu_stats stats{};
   uint32_t last_n = 0;
   uint32_t max_read_len = 1024;
@@ -2030,6 +2040,7 @@ struct kaiju_gpu_ctx {
     if (format && kj_format_free) kj_format_free(format);
     if (format_v && kj_fv_free) kj_fv_free(format_v);
     if (format_s && kj_fs_free) kj_fs_free(format_s);
+    if (format_n && kj_fn_free) kj_fn_free(format_n);
     DevBuf *all[] = {&fv_out, &fv_info, &fv_trunc, &fv_total, &fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
                      &vb_nacc, &vb_acc, &vb_tlen, &vb_text, &vb_bestv, &vb_bestv_retry, &vb_packed, &vb_pos,
                      &redo_bitmap, &redo_list, &redo_items, &redo_index, &redo_pool, &redo_work, &redo_cls};
@@ -3068,6 +3079,131 @@ extern "C" int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_g
                      static_cast<kaiju_gpu_format_info *>(ctx->fmt_info.p));
   if (rc) return rc;
   if ((rc = format_download(ctx, s, out_text, out_cap, info_format))) return rc;
+  if (info_format->overflow) return fail(KAIJU_GPU_ERR_ARG, "the output text needs more than out_cap bytes");
+  return KAIJU_GPU_OK;
+  });
+}
+
+// ---- the output lines with taxon names on the device (format_names.hip) ------------------------------------------
+static int no_format_names() {
+  if (!kj_fn_launch || !kaiju_gpu_taxon_names_max_annotation) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "this library was linked without format_names.hip");
+  return KAIJU_GPU_OK;
+}
+extern "C" uint64_t kaiju_gpu_format_names_bound(uint64_t bytes1, uint32_t n, const kaiju_gpu_taxon_names *names) {
+  const uint64_t most = names && kaiju_gpu_taxon_names_max_annotation ? kaiju_gpu_taxon_names_max_annotation(names) : 0;
+  return bytes1 + (uint64_t)n * (kjn::kNamesExtra + most);
+}
+// the passes on stream s; all pointers device pointers
+static int format_names_launch(kaiju_gpu_ctx *ctx, hipStream_t s, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
+                               const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names, const kaiju_gpu_taxon_names *names,
+                               int drop, void *d_out, uint64_t out_cap, kaiju_gpu_format_names_info *d_info) {
+  if (!names) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (kj_fn_device(names) != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "the taxon names live on another device");
+  if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup carry no taxon");
+  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
+  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
+  kjf::Params P{};
+  P.db_length = ctx->ix->info.db_length;
+  P.min_evalue = ctx->params.min_evalue;
+  P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
+  P.protein = ctx->params.input_is_protein ? 1 : 0;
+  P.paired = paired ? 1 : 0;
+  const char *err = "";
+  const int rc = kj_fn_launch(&ctx->format_n, s, P, static_cast<const double *>(ctx->fmt_pw.p), d_recs, d_off, n, d_text1, bytes1, d_names, names, drop,
+                              d_out, out_cap, d_info, &err);
+  return rc ? fail(rc, err) : KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_format_names_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
+                                             const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names,
+                                             const kaiju_gpu_taxon_names *names, int drop_unclassified, void *d_out, uint64_t out_cap,
+                                             kaiju_gpu_format_names_info *d_info, void *stream) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_names()) return rc;
+  if (!ctx) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  return format_names_launch(ctx, stream ? static_cast<hipStream_t>(stream) : ctx->stream, d_recs, d_off, n, paired, d_text1, bytes1, d_names, names,
+                             drop_unclassified, d_out, out_cap, d_info);
+  });
+}
+
+// *info and the bytes the passes wrote, from ctx->fmt_info / fmt_out to the host; blocks
+static int format_names_download(kaiju_gpu_ctx *ctx, hipStream_t s, char *out, uint64_t out_cap, kaiju_gpu_format_names_info *info) {
+  KJ_HIP(hipMemcpyAsync(info, ctx->fmt_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipStreamSynchronize(s));
+  uint64_t written = info->text_bytes;
+  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fn_written(ctx->format_n), sizeof written, hipMemcpyDeviceToHost));
+  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
+  if (written) KJ_HIP(hipMemcpy(out, ctx->fmt_out.p, written, hipMemcpyDeviceToHost));
+  return KAIJU_GPU_OK;
+}
+
+extern "C" int kaiju_gpu_format_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, int paired,
+                                      const char *text1, uint64_t bytes1, const kaiju_gpu_name_span *names_spans,
+                                      const kaiju_gpu_taxon_names *names, int drop_unclassified, char *out, uint64_t out_cap,
+                                      kaiju_gpu_format_names_info *info) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_names()) return rc;
+  if (!ctx || !info || !names || (n && (!recs || !off || !names_spans)) || (!text1 && bytes1) || (!out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (bytes1 > kjf::kMaxBytes || n > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes, a batch below 2^31 records");
+  KJ_HIP(hipSetDevice(ctx->ix->device));
+  int rc;
+  if ((rc = ensure(ctx->ing_text1, bytes1 + 64))) return rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
+  if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_names_info)))) return rc;
+  hipStream_t s = ctx->stream;
+  if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
+  if (n) {
+    KJ_HIP(hipMemcpyAsync(ctx->h_compact.p, recs, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names_spans, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+  }
+  rc = format_names_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired,
+                           ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), names, drop_unclassified,
+                           ctx->fmt_out.p, out_cap, static_cast<kaiju_gpu_format_names_info *>(ctx->fmt_info.p));
+  if (rc) return rc;
+  return format_names_download(ctx, s, out, out_cap, info);
+  });
+}
+
+extern "C" int kaiju_gpu_classify_text_to_text_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
+                                                     const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
+                                                     const kaiju_gpu_taxon_names *names, int drop_unclassified, char *out_text, uint64_t out_cap,
+                                                     kaiju_gpu_parse_info *info_parse, kaiju_gpu_format_names_info *info_format) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if (int rc = no_format_names()) return rc;
+  if (!ctx || !t || !names || !info_format || (!out_text && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
+  if (bytes1 > kjf::kMaxBytes) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes");
+  memset(info_format, 0, sizeof *info_format);
+  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info_parse)) return rc;
+  if (info_parse->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
+  const bool paired = text2 != nullptr;
+  const uint32_t n = reads_emitted(*info_parse, paired, rec_cap);
+  hipStream_t s = ctx->stream;
+  int rc;
+  if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
+  if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_names_info)))) return rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if (n) {
+    if ((rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info_parse->max_mate_len)))) return rc;
+    if ((rc = ensure(ctx->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
+    rc = kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info_parse->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), n,
+                                                 paired ? 1 : 0, static_cast<kaiju_gpu_hit *>(ctx->h_hits.p),
+                                                 static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), s);
+    if (rc) return rc;
+  }
+  rc = format_names_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired ? 1 : 0,
+                           ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), names, drop_unclassified,
+                           ctx->fmt_out.p, out_cap, static_cast<kaiju_gpu_format_names_info *>(ctx->fmt_info.p));
+  if (rc) return rc;
+  if ((rc = format_names_download(ctx, s, out_text, out_cap, info_format))) return rc;
   if (info_format->overflow) return fail(KAIJU_GPU_ERR_ARG, "the output text needs more than out_cap bytes");
   return KAIJU_GPU_OK;
   });

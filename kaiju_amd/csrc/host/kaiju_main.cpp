@@ -871,6 +871,27 @@ int main(int argc, char **argv) {
   const bool device_output = output_env && !strcmp(output_env, "device") && device_ingest;
   if (output_env && !strcmp(output_env, "device") && !device_output)
     fprintf(stderr, "KAIJU_GPU_OUTPUT=device is ignored: it needs KAIJU_GPU_INGEST=device and the three-column output of kaiju / kaiju-multi without -v\n");
+  // KAIJU_GPU_TAXON_NAMES=<names.dmp>: the device lines carry the column of kaiju-addTaxonNames (format_names.hip):
+  // KAIJU_GPU_TAXON_NAMES_MODE=name (default) | path (the tool's -p) | ranks:<list> (-r), KAIJU_GPU_TAXON_NAMES_DROP_U=1 (-u).
+  // The column exists in the device lines only: where they are not in effect the run ends instead of printing lines without it.
+  const char *tnames_env = getenv("KAIJU_GPU_TAXON_NAMES");
+  const bool taxon_names = tnames_env && *tnames_env;
+  int tnames_mode = KAIJU_NAMES_NAME;
+  std::string tnames_ranks;
+  const char *tnames_drop_env = getenv("KAIJU_GPU_TAXON_NAMES_DROP_U");
+  const bool tnames_drop = tnames_drop_env && !strcmp(tnames_drop_env, "1");
+  if (taxon_names) {
+    if (!device_output)
+      die(std::string("KAIJU_GPU_TAXON_NAMES needs the device output lines (KAIJU_GPU_INGEST=device KAIJU_GPU_OUTPUT=device, kaiju / kaiju-multi without -v): ") +
+          (xmode ? "kaijux / kaijup print no taxon" : verbose ? "the lines of -v are not made with names" : parse_only ? "KAIJU_GPU_PARSE_ONLY prints no lines" :
+           "the lines of this run are made on the host"));
+    const char *m = getenv("KAIJU_GPU_TAXON_NAMES_MODE");
+    const std::string mode_s = m ? m : "name";
+    if (mode_s == "path") tnames_mode = KAIJU_NAMES_PATH;
+    else if (mode_s.compare(0, 6, "ranks:") == 0) { tnames_mode = KAIJU_NAMES_RANKS; tnames_ranks = mode_s.substr(6); }
+    else if (mode_s != "name") die("KAIJU_GPU_TAXON_NAMES_MODE: name, path or ranks:<comma separated list>, not " + mode_s);
+  }
+  std::atomic<uint64_t> tnames_unknown{0}, tnames_unnamed{0};
   // KAIJU_GPU_VERBOSE_OUTPUT=device: with -v the device writes the seven-column lines (format_verbose.hip) and every piece of a
   // batch comes back as finished text.  kaiju / kaiju-multi only; ingest stays on the host.
   const char *vout_env = getenv("KAIJU_GPU_VERBOSE_OUTPUT");
@@ -917,6 +938,8 @@ int main(int argc, char **argv) {
   kaiju_gpu_index_info info;
   memset(&info, 0, sizeof info);
   std::vector<kaiju_gpu_taxonomy *> dtaxes((size_t)n_dev, nullptr);
+  kaiju_taxon_names *tnames = nullptr;
+  std::vector<kaiju_gpu_taxon_names *> dtnames((size_t)n_dev, nullptr);
   const int n_ctx = 2 * n_dev;              // per GPU two: copies of one batch overlap with kernels of the other
   std::vector<kaiju_gpu_ctx *> ctx((size_t)n_ctx, nullptr);
   // The index loads (and nodes.dmp is parsed, and the contexts are created) on a thread of its own while the input is
@@ -953,6 +976,14 @@ int main(int argc, char **argv) {
         rc = kaiju_gpu_taxonomy_upload(tax, devices[(size_t)d], &dtaxes[(size_t)d]);
         if (rc != 0) die(std::string("kaiju_gpu_taxonomy_upload: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
       }
+    if (taxon_names) {
+      rc = kaiju_taxon_names_load(nodes_fn.c_str(), tnames_env, tnames_mode, tnames_ranks.c_str(), &tnames);
+      if (rc != 0) die(std::string("KAIJU_GPU_TAXON_NAMES: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
+      for (int d = 0; d < n_dev; d++) {
+        rc = kaiju_gpu_taxon_names_upload(tnames, devices[(size_t)d], &dtnames[(size_t)d]);
+        if (rc != 0) die(std::string("kaiju_gpu_taxon_names_upload: ") + kaiju_gpu_strerror(rc) + " (" + kaiju_gpu_last_error() + ")");
+      }
+    }
     if (device_vout)
       for (int d = 0; d < n_dev; d++) {                    // (every replica: column 6 is made where the batch runs)
         rc = kaiju_gpu_index_upload_accessions(indexes[(size_t)d]);
@@ -1195,14 +1226,27 @@ int main(int argc, char **argv) {
             const RawBlock &ra = *b->raw_a;
             const RawBlock *rb = b->raw_b.get();
             const uint32_t cap = ra.n_records;
-            const uint64_t out_cap = kaiju_gpu_format_bound(ra.size, cap);
+            kaiju_gpu_taxon_names *dn = taxon_names ? dtnames[(size_t)(k / 2)] : nullptr;
+            const uint64_t out_cap = dn ? kaiju_gpu_format_names_bound(ra.size, cap, dn) : kaiju_gpu_format_bound(ra.size, cap);
             b->text.resize(out_cap);
             kaiju_gpu_parse_info pi;
             kaiju_gpu_format_info fi;
             memset(&pi, 0, sizeof pi);
             memset(&fi, 0, sizeof fi);
-            r = kaiju_gpu_classify_text_to_text(ctx[k], dtaxes[(size_t)(k / 2)], ra.text, ra.size, rb ? (rb->text ? rb->text : "") : nullptr,
-                                                rb ? rb->size : 0, ra.fastq ? 1 : 0, 0, cap, &b->text[0], out_cap, &pi, &fi);
+            if (dn) {
+              // ... with the column of kaiju-addTaxonNames (kaiju_gpu_classify_text_to_text_names)
+              kaiju_gpu_format_names_info fni;
+              memset(&fni, 0, sizeof fni);
+              r = kaiju_gpu_classify_text_to_text_names(ctx[k], dtaxes[(size_t)(k / 2)], ra.text, ra.size, rb ? (rb->text ? rb->text : "") : nullptr,
+                                                        rb ? rb->size : 0, ra.fastq ? 1 : 0, 0, cap, dn, tnames_drop ? 1 : 0, &b->text[0], out_cap, &pi, &fni);
+              fi.text_bytes = fni.text_bytes; fi.n_records = fni.n_records; fi.n_classified = fni.n_classified; fi.overflow = fni.overflow;
+              fi.n_inexact = fni.n_inexact;
+              tnames_unknown += fni.n_unknown_taxon;
+              tnames_unnamed += fni.n_unnamed_taxon;
+            } else {
+              r = kaiju_gpu_classify_text_to_text(ctx[k], dtaxes[(size_t)(k / 2)], ra.text, ra.size, rb ? (rb->text ? rb->text : "") : nullptr,
+                                                  rb ? rb->size : 0, ra.fastq ? 1 : 0, 0, cap, &b->text[0], out_cap, &pi, &fi);
+            }
             if (r == 0) {
               if (pi.n_records != ra.n_records || (rb && pi.n_records2 != rb->n_records))
                 die("internal error: the device found " + std::to_string(pi.n_records) + " / " + std::to_string(pi.n_records2) + " records in a block, the reader " +
@@ -1216,6 +1260,8 @@ int main(int argc, char **argv) {
               device_inexact = fi.n_inexact;
               n = 0;                                  // (no records came back: nothing to look through below)
             }
+          } else if (taxon_names) {
+            die("internal error: a batch without device output in a run with KAIJU_GPU_TAXON_NAMES");
           } else if (b->raw_a) {
             const RawBlock &ra = *b->raw_a;
             const RawBlock *rb = b->raw_b.get();
@@ -1383,6 +1429,10 @@ int main(int argc, char **argv) {
   }
   // (the host formatter warns read by read; the device reports a count)
   if (truncated_reads.load()) fprintf(stderr, "Warning: matched peptides of %llu reads truncated\n", (unsigned long long)truncated_reads.load());
+  if (tnames_unknown.load() || tnames_unnamed.load())
+    fprintf(stderr, "Warning: %llu classified reads kept their line without a name: the taxon of %llu is not in %s, the taxon of %llu has no scientific name in %s\n",
+            (unsigned long long)(tnames_unknown.load() + tnames_unnamed.load()), (unsigned long long)tnames_unknown.load(), nodes_fn.c_str(),
+            (unsigned long long)tnames_unnamed.load(), tnames_env);
   if (verbose) fprintf(stderr, "%s Finished.\n", now().c_str());
   if (getenv("KAIJU_GPU_STAGE_TIMES"))
     fprintf(stderr, "[CPU time per stage, summed over its threads] read %.3f s, parse %.3f s, gpu calls %.3f s, format %.3f s, "
@@ -1411,6 +1461,8 @@ int main(int argc, char **argv) {
   }
   for (int k = 0; k < n_ctx; k++) if (ctx[(size_t)k]) kaiju_gpu_destroy(ctx[(size_t)k]);
   for (kaiju_gpu_taxonomy *t : dtaxes) if (t) kaiju_gpu_taxonomy_free(t);
+  for (kaiju_gpu_taxon_names *t : dtnames) if (t) kaiju_gpu_taxon_names_free(t);
+  if (tnames) kaiju_taxon_names_free(tnames);
   for (kaiju_gpu_index *ix : indexes) if (ix) kaiju_gpu_index_free(ix);
   if (tax) kaiju_taxonomy_free(tax);
   wall_mark("teardown done");
