@@ -307,6 +307,13 @@ int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *
                           kaiju_gpu_seg_fragment *frags, uint64_t frag_cap, uint64_t *n_frags,
                           int32_t *lr, uint64_t lr_cap, uint64_t *n_lr);
 
+/* Diagnostics: the table the SEG kernels take s_Trim's window probabilities from (one double per multiset of letter counts,
+   computed on the host once per process) against the device's own arithmetic.  One kernel computes every entry again with
+   the function the table replaces and looks it up as the SEG pass does; *entries: entries of the table, *mismatches: those
+   whose key, presence or 64-bit pattern differs (0 on a working device).  The environment variable KAIJU_GPU_SEG_TABLE=0,
+   read when an index is loaded, makes the SEG kernels of that index compute every window directly; the check still runs. */
+int kaiju_gpu_seg_table_check(const kaiju_gpu_index *index, uint64_t *entries, uint64_t *mismatches);
+
 /* Diagnostics: the locate by itself.  Record r is given the suffix-array intervals first[r] .. first[r + 1] - 1 (at most 16:
    rows lo[i] .. lo[i] + len[i] - 1, len[i] >= 1) as the matches a search lane would have left in it, and the call runs the
    locate that a classification of this context would run on this index (the row -> taxon table, the sampled one, or the walk

@@ -260,6 +260,14 @@ class Index:
         _check(L.kaiju_gpu_index_digest(self._h, out.ctypes.data, len(out)))
         return {k: int(v) for k, v in zip(self.DIGEST_NAMES, out)}
 
+    def seg_table_check(self):
+        """kaiju_gpu_seg_table_check: (entries, mismatches) of the SEG window-probability table against the device's arithmetic"""
+        L = lib()
+        L.kaiju_gpu_seg_table_check.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, bad = C.c_uint64(), C.c_uint64()
+        _check(L.kaiju_gpu_seg_table_check(self._h, C.byref(n), C.byref(bad)))
+        return int(n.value), int(bad.value)
+
     def layout(self) -> IndexLayout:
         """kaiju_gpu_index_get_layout: bytes of every array this index holds in HBM (INDEX_ARRAYS order) and its scalars"""
         L = lib()

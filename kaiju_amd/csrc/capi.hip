@@ -352,6 +352,17 @@ struct CoopWave {
   __device__ __forceinline__ void sync() const { __syncthreads(); }     // (the block is one wavefront)
   __device__ __forceinline__ int lane() const { return (int)(threadIdx.x & 63u); }
   __device__ __forceinline__ int width() const { return 64; }
+  // the packed counts (kj_core.h: six bits a letter, ten letters a word) of the letters `a` (0 .. 19; anything else: none) of
+  // the lanes BELOW this one: per letter one ballot and the count of its bits below the lane (seg_trim's prefix counts)
+  __device__ __forceinline__ void prefix_counts(uint32_t a, uint64_t &c0, uint64_t &c1) const {
+    c0 = c1 = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < 20; x++) {
+      const uint64_t m = __ballot(a == x);
+      const uint64_t n = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (x < 10) c0 |= n << (6 * x); else c1 |= n << (6 * (x - 10));
+    }
+  }
   __device__ __forceinline__ void reduce_min(double &prob, int &t) const {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -384,7 +395,8 @@ struct CoopTeam {
 // SEG pass: one wavefront (= one 64-thread block at a time) per fragment that stage 1 flagged; the
 // fragment is copied to LDS first.  The number of fragments lives in device memory.
 constexpr int kSegBlock = 64, kSegStage = 2048;
-__global__ void __launch_bounds__(kSegBlock)
+// (four wavefronts per SIMD: 128 registers, no scratch; left to itself the compiler takes 139 and three - profiles/seg_prob_table)
+__global__ void __launch_bounds__(kSegBlock, 4)
 k_seg(Params p, SegTables st, Batch b, SegQueue sq) {
   __shared__ int64_t s_entg[13];
   __shared__ double s_lnf[kSegLnf];
@@ -393,8 +405,10 @@ k_seg(Params p, SegTables st, Batch b, SegQueue sq) {
   __shared__ uint8_t s_cls[kSegStage];
   if (threadIdx.x < 13) s_entg[threadIdx.x] = st.ent_g[threadIdx.x];
   if (threadIdx.x < kSegLnf) s_lnf[threadIdx.x] = st.lnfact[threadIdx.x];
+  __shared__ uint64_t s_keyw[kSegKeyWords];        // key words of the window-probability table (seg_prob_lookup)
+  if (threadIdx.x < kSegKeyWords) s_keyw[threadIdx.x] = st.ptab ? st.ptab_T[threadIdx.x] : 0;
   __syncthreads();
-  const SegCtx cx = seg_ctx(st, s_entg, s_lnf);
+  const SegCtx cx = seg_ctx(st, s_entg, s_lnf, s_keyw);
   __shared__ uint64_t s_pref[2 * (kSegPacked + 1)];
   CoopWave coop;
   coop.prefix = s_pref;
@@ -423,8 +437,10 @@ k_seg_teams(Params p, SegTables st, Batch b, SegQueue sq) {
   __shared__ uint8_t s_cls[kSegStage];
   if (threadIdx.x < 13) s_entg[threadIdx.x] = st.ent_g[threadIdx.x];
   if (threadIdx.x < kSegLnf) s_lnf[threadIdx.x] = st.lnfact[threadIdx.x];
+  __shared__ uint64_t s_keyw[kSegKeyWords];        // key words of the window-probability table (seg_prob_lookup)
+  if (threadIdx.x < kSegKeyWords) s_keyw[threadIdx.x] = st.ptab ? st.ptab_T[threadIdx.x] : 0;
   __syncthreads();
-  const SegCtx cx = seg_ctx(st, s_entg, s_lnf);
+  const SegCtx cx = seg_ctx(st, s_entg, s_lnf, s_keyw);
   __shared__ uint64_t s_pref[NT * 2 * (kSegPacked + 1)];
   const uint32_t team = threadIdx.x / (uint32_t)T;
   CoopTeam<T> coop;
@@ -1081,8 +1097,10 @@ struct kaiju_gpu_index {
   ConstTables ct_host{};
   ConstTables *d_ct = nullptr;
   const Stage1Tables *d_s1 = nullptr;
-  SegTables st{};                 // lnfact points to device memory
+  SegTables st{};                 // lnfact, ptab and ptab_T point to device memory
   double *d_lnfact = nullptr;
+  const SegProbEntry *d_ptab = nullptr;      // the window-probability table of s_Trim and its key words (also with KAIJU_GPU_SEG_TABLE=0)
+  const uint64_t *d_ptab_T = nullptr;
   std::vector<void *> allocs;
   kaiju_gpu_index_info info{};
   kaiju_gpu_index_footprint fp{};
@@ -1310,6 +1328,20 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
   const double *dl = nullptr;
   if ((rc = upload(ix.get(), lnfact, &dl))) return rc;
   ix->st.lnfact = dl;
+  // the window-probability table of s_Trim: no index data (not in kj::index_arrays, the digest or the image).
+  // KAIJU_GPU_SEG_TABLE=0: the SEG kernels compute every window directly
+  uint64_t seg_tab_bytes = 0;
+  {
+    const SegProbTable &pt = seg_prob_table();
+    const std::vector<uint64_t> keyw(pt.T, pt.T + kSegKeyWords);
+    if ((rc = upload(ix.get(), pt.slots, &ix->d_ptab))) return rc;
+    if ((rc = upload(ix.get(), keyw, &ix->d_ptab_T))) return rc;
+    seg_tab_bytes = pt.slots.size() * sizeof(SegProbEntry) + keyw.size() * 8;
+    const char *e = getenv("KAIJU_GPU_SEG_TABLE");
+    const bool off = ix->st.ptab == nullptr || (e && atoi(e) == 0);
+    ix->st.ptab = off ? nullptr : ix->d_ptab;
+    ix->st.ptab_T = off ? nullptr : ix->d_ptab_T;
+  }
   {
     std::vector<Stage1Tables> s1(1);
     build_stage1_tables(ix->ct_host, ix->st, s1[0]);
@@ -1662,7 +1694,7 @@ static int index_from_packed(PackedIndex &pk, int device_id, kaiju_gpu_index **o
     uint64_t nlw = 1;
     for (uint32_t q = 1; q < d.kline_k; q++) nlw *= 20;
     f.kmer_lines = d.kline ? nlw * kKLineBytes : 0;
-    f.other = sizeof(ConstTables) + sizeof(Stage1Tables) + lnfact.size() * 8;
+    f.other = sizeof(ConstTables) + sizeof(Stage1Tables) + lnfact.size() * 8 + seg_tab_bytes;
     f.text = d.text ? text_bytes : 0;
     ix->tpos_bytes = d.sa_tpos5 ? tpos_bytes : 0;
     f.sa_full = d.sa_full ? pk.bwtlen * 8 : (d.sa_tpos5 ? tpos_bytes : 0) + (d.mb_base && (d.row_tax || d.row_tax_s) ? rowtax_bytes : 0);   // (+ the taxon of every row, DevIndex::row_tax; wide: the text positions + that table, or the sampled one: row_tax_s)
@@ -3726,6 +3758,68 @@ extern "C" int kaiju_gpu_get_op_counts(kaiju_gpu_ctx *ctx, uint64_t *out, uint32
   KJ_HIP(hipMemcpy(v, static_cast<const uint32_t *>(ctx->counters.p) + kCntOpTotals, sizeof v, hipMemcpyDeviceToHost));
   for (uint32_t x = 0; x < n_out && x < (uint32_t)kOpcN; x++) out[x] = v[x];
   return KAIJU_GPU_OK;
+}
+
+// Diagnostics: the window-probability table of s_Trim as the device holds it against the device's own arithmetic
+// (include/kaiju_gpu.h): every entry is looked up (seg_prob_lookup) and computed (seg_prob_of_counts) from the counts the host
+// made it from; out[0] entries, out[1] those whose key, presence or bit pattern differs
+__global__ void __launch_bounds__(256)
+k_seg_table_check(SegTables st, const uint64_t *reps, const uint8_t *rep_len, uint32_t slots, uint32_t *out) {
+  __shared__ int64_t s_entg[13];
+  __shared__ double s_lnf[kSegLnf];
+  __shared__ uint64_t s_keyw[kSegKeyWords];
+  if (threadIdx.x < 13) s_entg[threadIdx.x] = st.ent_g[threadIdx.x];
+  if (threadIdx.x < kSegLnf) s_lnf[threadIdx.x] = st.lnfact[threadIdx.x];
+  if (threadIdx.x < kSegKeyWords) s_keyw[threadIdx.x] = st.ptab_T[threadIdx.x];
+  __syncthreads();
+  const SegCtx cx = seg_ctx(st, s_entg, s_lnf, s_keyw);
+  uint32_t entries = 0, bad = 0;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < slots; i += gridDim.x * 256) {
+    const int l = rep_len[i];
+    const SegProbEntry e = st.ptab[i];
+    if (l == 0) { bad += e.key != 0; continue; }
+    entries++;
+    const uint64_t c0 = reps[2 * (size_t)i], c1 = reps[2 * (size_t)i + 1];
+    const double direct = seg_prob_of_counts(cx, c0, c1, l);
+    double got = 0.;
+    const bool found = seg_prob_lookup(cx, c0, c1, got);
+    bad += !found || e.key != seg_counts_key(s_keyw, c0, c1) || __double_as_longlong(got) != __double_as_longlong(direct) ||
+           __double_as_longlong(e.val) != __double_as_longlong(direct);
+  }
+  if (entries) atomicAdd(out, entries);
+  if (bad) atomicAdd(out + 1, bad);
+}
+extern "C" int kaiju_gpu_seg_table_check(const kaiju_gpu_index *ix, uint64_t *entries, uint64_t *mismatches) {
+  return guarded([&]() -> int {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KAIJU_GPU_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
+  if (!ix || !entries || !mismatches) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  *entries = *mismatches = 0;
+  KJ_HIP(hipSetDevice(ix->device));
+  const SegProbTable &pt = seg_prob_table();
+  const uint32_t slots = (uint32_t)pt.slots.size();
+  if (!ix->d_ptab || slots == 0) return fail(KAIJU_GPU_ERR_ARG, "the index holds no window-probability table");
+  SegTables st = ix->st;                           // (the table of the index also where KAIJU_GPU_SEG_TABLE=0 keeps the kernels off it)
+  st.ptab = ix->d_ptab; st.ptab_T = ix->d_ptab_T; st.ptab_mask = pt.mask; st.ptab_probe = pt.probe; st.ptab_max = (uint32_t)kSegTabMax;
+  uint8_t *buf = nullptr;
+  const size_t reps_bytes = pt.reps.size() * 8;
+  KJ_HIP(hipMalloc((void **)&buf, reps_bytes + slots + 16));
+  hipError_t e = hipMemcpy(buf, pt.reps.data(), reps_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(buf + reps_bytes, pt.rep_len.data(), slots, hipMemcpyHostToDevice);
+  uint32_t *d_out = reinterpret_cast<uint32_t *>(buf + reps_bytes + ((slots + 7u) & ~7u));
+  if (e == hipSuccess) e = hipMemset(d_out, 0, 8);
+  uint32_t h[2] = {0, 0};
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_seg_table_check, dim3((slots + 255) / 256), dim3(256), 0, 0, st, reinterpret_cast<const uint64_t *>(buf),
+                       buf + reps_bytes, slots, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(h, d_out, sizeof h, hipMemcpyDeviceToHost);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return fail(KAIJU_GPU_ERR_HIP, hipGetErrorString(e));
+  *entries = h[0]; *mismatches = h[1];
+  return KAIJU_GPU_OK;
+  });
 }
 
 // Diagnostics: what the device SEG pass computed for every fragment of a batch of protein reads (include/kaiju_gpu.h).

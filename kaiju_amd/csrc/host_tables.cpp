@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "../../include/kaiju_gpu.h"
 
@@ -118,7 +119,74 @@ bool check_partitions(int remaining, int maxpart, int *sv, int n, const SegTable
   }
   return true;
 }
+
+// every partition of `remaining` into parts <= maxpart, at most 20 parts in all: part k becomes the count of letter k
+void fill_partitions(int remaining, int maxpart, int *sv, int n, const SegCtx &cx, SegProbTable &t) {
+  if (remaining == 0) {
+    int l = 0;
+    uint64_t c0 = 0, c1 = 0;
+    for (int a = 0; a < n; a++) {
+      l += sv[a];
+      if (a < 10) c0 += (uint64_t)sv[a] << (6 * a); else c1 += (uint64_t)sv[a] << (6 * (a - 10));
+    }
+    const uint64_t key = seg_counts_key(t.T, c0, c1);
+    if (key == 0) { t.error = "SEG window table: a multiset has the key of an empty slot"; return; }
+    uint32_t slot = (uint32_t)key & t.mask, looked = 1;
+    for (; t.slots[slot].key; slot = (slot + 1u) & t.mask, looked++)
+      if (t.slots[slot].key == key) { t.error = "SEG window table: two multisets of letter counts share a key"; return; }
+    t.slots[slot].key = key;
+    t.slots[slot].val = seg_prob_of_counts(cx, c0, c1, l);
+    t.reps[2 * (size_t)slot] = c0; t.reps[2 * (size_t)slot + 1] = c1;
+    t.rep_len[slot] = (uint8_t)l;
+    if (looked > t.probe) t.probe = looked;
+    t.entries++;
+    return;
+  }
+  if (n == 20) return;
+  for (int p = remaining < maxpart ? remaining : maxpart; p >= 1 && t.error.empty(); p--) {
+    sv[n] = p;
+    fill_partitions(remaining - p, p, sv, n + 1, cx, t);
+  }
+}
+uint64_t count_partitions(int remaining, int maxpart, int n) {
+  if (remaining == 0) return 1;
+  if (n == 20) return 0;
+  uint64_t c = 0;
+  for (int p = remaining < maxpart ? remaining : maxpart; p >= 1; p--) c += count_partitions(remaining - p, p, n + 1);
+  return c;
+}
+SegProbTable make_seg_prob_table(const SegTables &st) {
+  SegProbTable t;
+  // the key words: splitmix64 from a fixed seed
+  uint64_t x = 0x5e6f5eb1a57ab1e5ull;
+  t.T[0] = 0;
+  for (int v = 1; v < kSegKeyWords; v++) {
+    uint64_t z = (x += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    t.T[v] = z ^ (z >> 31);
+  }
+  uint64_t n = 0;
+  for (int l = 1; l <= kSegTabMax; l++) n += count_partitions(l, l, 0);
+  uint32_t size = 1;
+  while (size < 2 * n) size <<= 1;              // load <= 0.5
+  t.mask = size - 1;
+  t.slots.assign(size, SegProbEntry{0, 0.0});
+  t.reps.assign(2 * (size_t)size, 0);
+  t.rep_len.assign(size, 0);
+  const SegCtx cx = seg_ctx(st, st.ent_g, st.lnfact);      // (windows of at most kSegPacked residues: the head of ln(n!) only)
+  int sv[20];
+  for (int l = 1; l <= kSegTabMax && t.error.empty(); l++) fill_partitions(l, l, sv, 0, cx, t);
+  if (t.error.empty() && t.entries != n) t.error = "SEG window table: entry count";
+  return t;
+}
 }  // namespace
+
+namespace {
+std::once_flag g_seg_prob_once;
+SegProbTable g_seg_prob;          // made by the first build_seg_tables, read-only afterwards
+}  // namespace
+const SegProbTable &seg_prob_table() { return g_seg_prob; }
 
 int build_seg_tables(std::vector<double> &lnfact_host, SegTables &st, std::string &msg) {
   // blast_seg.c:52-1308 tabulates ln(n!) for n = 0..10000 printed with six decimals
@@ -146,6 +214,14 @@ int build_seg_tables(std::vector<double> &lnfact_host, SegTables &st, std::strin
   st.ent_locut32 = (int32_t)floor(scale32 * 2.2);
   int sv[16];
   if (!check_partitions(12, 12, sv, 0, st, msg)) return KAIJU_GPU_ERR_ARG;
+  // the window-probability table of s_Trim: every process computes the same one (ln(n!) above is the same for every caller)
+  st.ptab = nullptr; st.ptab_T = nullptr; st.ptab_mask = st.ptab_probe = st.ptab_max = 0;
+  std::call_once(g_seg_prob_once, [&] { g_seg_prob = make_seg_prob_table(st); });
+  if (!g_seg_prob.error.empty()) { msg = g_seg_prob.error; return KAIJU_GPU_ERR_ARG; }
+#ifndef KJ_SEG_NO_TABLE
+  st.ptab = g_seg_prob.slots.data(); st.ptab_T = g_seg_prob.T;
+  st.ptab_mask = g_seg_prob.mask; st.ptab_probe = g_seg_prob.probe; st.ptab_max = (uint32_t)kSegTabMax;
+#endif
   return 0;
 }
 

@@ -331,6 +331,10 @@ struct Hit {                 // == kaiju_gpu_hit
   uint64_t taxid[kMaxIds];
 };
 
+// One entry of the window-probability table of s_Trim (seg_prob_lookup): the key of a multiset of letter counts and the ln P0
+// seg_prob_of_counts returns for it; key 0: the slot is empty
+struct alignas(16) SegProbEntry { uint64_t key; double val; };
+
 // SEG tables built on the host (host_tables.cpp)
 struct SegTables {
   const double *lnfact;      // ln(n!) rounded to 6 decimals, blast_seg.c:52-1308
@@ -339,6 +343,11 @@ struct SegTables {
   int64_t ent_locut, ent_hicut;   // thresholds in the same fixed-point scale
   int32_t ent_g32[17];       // (13 used) the same at a 32-bit scale: enough to decide H <= locut (stage 1's trigger test)
   int32_t ent_locut32;
+  // ln P0 of every multiset of letter counts of windows of up to ptab_max residues (open addressing, slot = low bits of the
+  // key, at most ptab_probe slots looked at); ptab == nullptr: every window is computed directly
+  const SegProbEntry *ptab;
+  const uint64_t *ptab_T;    // [kSegKeyWords] key word of every count value, [0] = 0
+  uint32_t ptab_mask, ptab_probe, ptab_max;
 };
 
 // Constant tables (ConsumerThread.cpp:6-187); the kernels keep a copy in LDS.
@@ -616,8 +625,23 @@ constexpr int kSegWindow = 12, kSegDown = 5, kSegUp = 7, kSegMaxTrim = 50;
 constexpr int kSegMaxRegions = 32;
 constexpr int kSegPacked = 63;         // windows up to this length use the packed-count path
 constexpr int kSegLnf = 64;            // ln(n!) entries mirrored in LDS
+constexpr int kSegKeyWords = 64;       // key words of the window-probability table: one per value of a 6-bit count
+#ifndef KJ_SEG_TAB_MAX
+#define KJ_SEG_TAB_MAX 32
+#endif
+constexpr int kSegTabMax = KJ_SEG_TAB_MAX;   // the table holds the windows of up to this many residues
+static_assert(kSegTabMax >= 1 && kSegTabMax <= kSegPacked, "the table's windows are packed-count windows");
 
 #define KJ_SL(s, i) ((uint32_t)(s)[(i)] - 1u)
+
+// (host-side workload histograms of s_Trim, tests and tests/tools only: -DKJ_SEG_HIST.  [0] raw segment lengths, window lengths
+//  [1] served by the table, [2] computed on the prefix-count path, [3] computed on the other paths)
+#if defined(KJ_SEG_HIST) && !defined(__HIP_DEVICE_COMPILE__)
+extern unsigned long long kj_seg_hist[4][64];
+#define KJ_SEG_HISTO(h, v) kj_seg_hist[h][(v) < 63 ? (v) : 63]++
+#else
+#define KJ_SEG_HISTO(h, v)
+#endif
 
 struct SegCtx {                        // tables as the SEG code sees them (LDS copies on the device)
   const int64_t *ent_g;                // [13]
@@ -625,10 +649,16 @@ struct SegCtx {                        // tables as the SEG code sees them (LDS 
   const double *lnf;                   // [kSegLnf] head of the ln(n!) table
   const double *lnfact;                // whole table (global memory)
   uint32_t lnfact_n;
+  const SegProbEntry *tab;             // SegTables::ptab (global memory) or nullptr
+  const uint64_t *tab_T;               // [kSegKeyWords] its key words
+  uint32_t tab_mask, tab_probe, tab_max;
 };
-KJ_HD SegCtx seg_ctx(const SegTables &st, const int64_t *ent_g, const double *lnf) {
+// (key_words: where the kernel keeps a copy of SegTables::ptab_T; the host reads the table's own)
+KJ_HD SegCtx seg_ctx(const SegTables &st, const int64_t *ent_g, const double *lnf, const uint64_t *key_words = nullptr) {
   SegCtx c; c.ent_g = ent_g; c.ent_locut = st.ent_locut; c.ent_hicut = st.ent_hicut;
   c.lnf = lnf; c.lnfact = st.lnfact; c.lnfact_n = st.lnfact_n;
+  c.tab = st.ptab; c.tab_T = key_words ? key_words : st.ptab_T;
+  c.tab_mask = st.ptab_mask; c.tab_probe = st.ptab_probe; c.tab_max = st.ptab_max;
   return c;
 }
 
@@ -732,6 +762,26 @@ KJ_HD double seg_prob_of_counts(const SegCtx &cx, uint64_t c0, uint64_t c1, int 
   if (nz > 0 && nz < 20) ans1 -= cx.lnf[20 - nz];
   return seg_finish_prob(ans1, ans2, l);
 }
+// The key of the multiset of the 20 counts: the sum of one fixed word per count value (mod 2^64), whatever letter has it.  ln P0
+// is a function of that multiset alone - seg_prob_of_counts looks at "how many letters occur v times", never at which - and
+// the host has checked that no two multisets of the table share a key (host_tables.cpp)
+KJ_HD uint64_t seg_counts_key(const uint64_t *T, uint64_t c0, uint64_t c1) {
+  uint64_t key = 0;
+  for (int f = 0; f < 10; f++) key += T[(uint32_t)(c0 >> (6 * f)) & 63u] + T[(uint32_t)(c1 >> (6 * f)) & 63u];
+  return key;
+}
+// ln P0 from the table: the double seg_prob_of_counts returned on the host for these counts (any order of the letters).
+// false: not in the table (the caller computes it)
+KJ_HD bool seg_prob_lookup(const SegCtx &cx, uint64_t c0, uint64_t c1, double &prob) {
+  const uint64_t key = seg_counts_key(cx.tab_T, c0, c1);
+  uint32_t slot = (uint32_t)key & cx.tab_mask;
+  for (uint32_t n = 0; n < cx.tab_probe; n++, slot = (slot + 1u) & cx.tab_mask) {
+    const SegProbEntry e = cx.tab[slot];
+    if (e.key == key) { prob = e.val; return true; }
+    if (e.key == 0) break;
+  }
+  return false;
+}
 // the same for windows of any length
 KJ_HD double seg_window_prob_generic(const SegCtx &cx, const uint8_t *s, int l, int i) {
   uint32_t comp[20];
@@ -755,6 +805,14 @@ KJ_HD double seg_window_prob_generic(const SegCtx &cx, const uint8_t *s, int l, 
   return seg_finish_prob(ans1, ans2, l);
 }
 
+// a cooperation type with prefix_counts(a, c0, c1) (lane j brings letter a and receives the packed counts of the letters of
+// the lanes below it: the device's CoopWave) gets seg_trim's prefix counts in one step; the others count letter by letter
+template <class Coop, class = void> struct SegCoopCounts { static constexpr bool value = false; };
+template <class Coop>
+struct SegCoopCounts<Coop, decltype((void)static_cast<const Coop *>(nullptr)->prefix_counts(0u, *static_cast<uint64_t *>(nullptr), *static_cast<uint64_t *>(nullptr)))> {
+  static constexpr bool value = true;
+};
+
 // s_Trim (blast_seg.c:1971-2015) on s[0..len): trimmed [lend, rend] relative to s.  The reference
 // visits window lengths len, len-1, ..., minlen+1 and for each all start positions left to right,
 // keeping a window only if its probability is strictly smaller than the best so far; with the
@@ -769,29 +827,67 @@ KJ_HD void seg_trim(const SegCtx &cx, const Coop &coop, const uint8_t *s, int le
   int best_t = 0x7fffffff;
   int d = 0, base = 0;                            // base = d(d+1)/2 <= t
   // The counts of a sub-window are the difference of two PREFIX counts of the raw segment (fields of six bits, no borrows: a
-  // prefix count never falls): pref[2j], pref[2j + 1] = the packed counts of s[0 .. j), written once per call - lane j counts
-  // its j letters - where every one of the len (len - 1) / 2 sub-windows used to count its own (a third of the instructions
-  // of this function, which is where the SEG pass spends its time: profiles/r06_seg_teams)
+  // prefix count never falls): pref[2j], pref[2j + 1] = the packed counts of s[0 .. j), written once per call - by the lanes
+  // together (SegCoopCounts), or lane j counts its j letters - where every one of the len (len - 1) / 2 sub-windows used to
+  // count its own (a third of the instructions of this function: profiles/r06_seg_teams)
   uint64_t *pref = len <= kSegPacked ? coop.pref() : nullptr;
+  KJ_SEG_HISTO(0, len);
   if (pref) {
     coop.sync();                                  // (the previous call's prefix counts are no longer read)
-    for (int j = coop.lane(); j <= len; j += coop.width()) {
-      uint64_t c0 = 0, c1 = 0;
-      for (int k = 0; k < j; k++) {
-        const uint32_t a = KJ_SL(s, k);
-        if (a < 10) c0 += 1ull << (6 * a); else c1 += 1ull << (6 * (a - 10));
+    if constexpr (SegCoopCounts<Coop>::value) {
+      // lane j brings letter j and receives the counts of s[0 .. j) (len <= 63: a lane per letter and one for the whole)
+      const int j = coop.lane();
+      uint64_t c0, c1;
+      coop.prefix_counts(j < len ? KJ_SL(s, j) : 0xffu, c0, c1);
+      if (j <= len) { pref[2 * j] = c0; pref[2 * j + 1] = c1; }
+    } else {
+      for (int j = coop.lane(); j <= len; j += coop.width()) {
+        uint64_t c0 = 0, c1 = 0;
+        for (int k = 0; k < j; k++) {
+          const uint32_t a = KJ_SL(s, k);
+          if (a < 10) c0 += 1ull << (6 * a); else c1 += 1ull << (6 * (a - 10));
+        }
+        pref[2 * j] = c0; pref[2 * j + 1] = c1;
       }
-      pref[2 * j] = c0; pref[2 * j + 1] = c1;
     }
     coop.sync();
   }
-  for (int t = coop.lane(); t < W; t += coop.width()) {
+  // The windows of at most cx.tab_max residues - t >= t_tab: the lengths fall with t - take ln P0 from the table, in a loop of
+  // their own so that the registers of the two ways are never live together.  A lane that does not find a key (no such key
+  // exists: the table holds every multiset of these lengths) computes all its windows as if there were no table
+  int t_direct = W;                                // this lane computes its windows t < t_direct
+  double tab_best = 1.;
+  int tab_best_t = 0x7fffffff;
+#ifndef KJ_SEG_NO_TABLE
+  if (pref && cx.tab) {
+    int dt = len > (int)cx.tab_max ? len - (int)cx.tab_max : 0;
+    if (dt > D) dt = D;
+    const int t_tab = dt * (dt + 1) / 2;
+    int bt = t_tab;                                // = dt (dt + 1) / 2 <= t
+    const int w = coop.width();
+    int t = coop.lane() >= t_tab ? coop.lane() : coop.lane() + (t_tab - coop.lane() + w - 1) / w * w;
+    bool missed = false;
+    for (; t < W; t += w) {
+      while (bt + dt + 1 <= t) { bt += dt + 1; dt++; }
+      const int i = t - bt, l = len - dt;
+      double prob;
+      if (!seg_prob_lookup(cx, pref[2 * (i + l)] - pref[2 * i], pref[2 * (i + l) + 1] - pref[2 * i + 1], prob)) { missed = true; break; }
+      KJ_SEG_HISTO(1, l);
+      if (prob < tab_best) { tab_best = prob; tab_best_t = t; }
+    }
+    if (missed) { tab_best = 1.; tab_best_t = 0x7fffffff; }
+    else t_direct = t_tab;
+  }
+#endif
+  for (int t = coop.lane(); t < t_direct; t += coop.width()) {
     while (base + d + 1 <= t) { base += d + 1; d++; }
     const int i = t - base, l = len - d;
+    KJ_SEG_HISTO(pref ? 2 : 3, l);
     const double prob = pref ? seg_prob_of_counts(cx, pref[2 * (i + l)] - pref[2 * i], pref[2 * (i + l) + 1] - pref[2 * i + 1], l)
                         : l <= kSegPacked ? seg_window_prob_packed(cx, s, l, i) : seg_window_prob_generic(cx, s, l, i);
     if (prob < best) { best = prob; best_t = t; }
   }
+  if (tab_best < best) { best = tab_best; best_t = tab_best_t; }    // (the table's windows come later in the visiting order)
   coop.reduce_min(best, best_t);
   int lend = 0, rend = len - 1;
   if (best_t != 0x7fffffff) {
