@@ -46,8 +46,25 @@ def build_mkfmi(force=False, verbose=False):
     return MKFMI_LIB
 
 
+MKFMI_GPU_LIB = os.path.join(HERE, "libkaiju_mkfmi_gpu.so")
+MKFMI_GPU_SRC = [os.path.join(CSRC, f) for f in ("mkfmi.cpp", "sufsort.hip", "mkfmi.h", "kj_sufsort.h")]
+
+
+def build_mkfmi_gpu(force=False, verbose=False):
+    """the index builder with the suffix sort on the device (csrc/kj_sufsort.h): the host builder's source with a define plus
+    sufsort.hip, a third library - libkaiju_mkfmi.so stays free of HIP and libkaiju_gpu.so free of the builder"""
+    if force or not os.path.exists(MKFMI_GPU_LIB) or any(os.path.getmtime(d) > os.path.getmtime(MKFMI_GPU_LIB) for d in MKFMI_GPU_SRC):
+        cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc", "-Wno-unused-result",
+               "-DKAIJU_MKFMI_GPU", "-o", MKFMI_GPU_LIB] + MKFMI_GPU_SRC[:2] + ["-lpthread"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+    return MKFMI_GPU_LIB
+
+
 def build(force=False, verbose=False):
     build_mkfmi(force=force, verbose=verbose)
+    build_mkfmi_gpu(force=force, verbose=verbose)
     if force or needs_build():
         cmd = [hipcc_path()] + FLAGS + ["-o", LIB] + [os.path.join(CSRC, s) for s in SOURCES] + ["-lpthread", "-ldl"]
         if verbose:

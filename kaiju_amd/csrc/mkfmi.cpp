@@ -17,8 +17,10 @@
 //   * sequence names/lengths are stored in sorted-sequence order (SortSeqs, mkbwt.c:700-733);
 //   * FMI: index1 every 2^16, index2 every 2^8, BWT bytes re-coded as (letter, in-block count)
 //     with the code table of find_startLcode (compactfmi.c:108-150).
-// Suffixes are sorted bucket-wise (first two letters) with std::sort on a word-at-a-time
-// comparator, buckets in parallel.
+// Suffixes are sorted bucket-wise (first three symbols) with std::sort on a word-at-a-time
+// comparator, buckets in parallel (sort_suffixes_host) - or, compiled with -DKAIJU_MKFMI_GPU into
+// libkaiju_mkfmi_gpu.so and asked to, on a GPU (sort_suffixes_device: kj_sufsort.h, sufsort.hip).
+// Everything behind the sorted suffix array is the same host code either way.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -36,6 +38,9 @@
 #include <vector>
 
 #include "mkfmi.h"
+#ifdef KAIJU_MKFMI_GPU
+#include "kj_sufsort.h"
+#endif
 
 namespace {
 
@@ -249,36 +254,10 @@ struct SufLess {
   }
 };
 
-// copies > 1: the index of the database in which every sequence of the FASTA file occurs `copies` times in a row (copy t of
-// sequence i is sequence i * copies + t of that database) - WITHOUT sorting it again: equal suffixes of different sequences
-// compare by file order, so row r of the index of the file becomes the rows r * copies .. r * copies + copies - 1.  The output
-// is byte for byte what this builder (and the reference's) writes for the FASTA with the repeats spelled out
-// (tests/test_mkfmi_pin.py); a 2^32-row index for the tests of the wide path takes half a minute this way instead of the
-// seven minutes of sorting 4.3 G suffixes.  copy_taxids (optional): copy t of a sequence named X_<id> is named
-// X_<copy_taxids[(i + t) % n]>, so that the copies do not all carry one taxon.
+// ---- the suffix sort: two implementations of "fill SA[0, nsuf) with the letter positions in suffix order" --------------------
+// on the host: bucket the suffixes by their first three symbols, std::sort per bucket on the threads
 template <class I>
-int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t copies = 1, const uint64_t *copy_taxids = nullptr,
-          uint32_t n_copy_taxids = 0) {
-  // alphabet of kaiju-makedb:373 with the terminator in front (mkbwt.c:read_alphabet)
-  const char alphabet[] = "*ACDEFGHIKLMNPQRSTVWY";
-  const int alen = 21;
-  signed char trans[128];
-  trans[0] = 0;
-  for (int i = 1; i < 128; i++) trans[i] = isalpha(i) ? (signed char)(alen - 1) : (signed char)-1;
-  for (int i = 0; i < alen; i++) { trans[toupper(alphabet[i])] = (signed char)i; trans[tolower(alphabet[i])] = (signed char)i; }
-  // the reference's table maps the terminator character itself ('*') to code 0, i.e. a '*' inside
-  // the FASTA would plant a terminator in the middle of a sequence; it is skipped here
-  trans[(int)'*'] = -1;
-  std::vector<Seq> seqs;
-  RawArr<uint8_t> T;
-  BuildClock bc;
-  const unsigned nt = (unsigned)std::max(1, threads);
-  uint64_t tlen = 0;                              // == bwtlen of the file's own index
-  if (!read_fasta(faa, trans, nt, seqs, T, tlen)) return KAIJU_GPU_ERR_IO;
-  const uint64_t nseq = seqs.size();
-  bc.mark("read FASTA");
-  if (sizeof(I) == 4 && tlen >= 0xfffffff0ull) { g_err = "internal: index type too small"; return KAIJU_GPU_ERR_ARG; }
-
+int sort_suffixes_host(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, unsigned nt, RawArr<I> &SA, BuildClock &bc) {
   // ---- bucket the letter suffixes by their first three symbols (what follows a terminator reads as terminators: the
   //      suffixes of a bucket whose key ends in a terminator are equal and stay in file order) ---------------------------
   const int NB = 21 * 21 * 21;
@@ -298,9 +277,7 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
     bstart[k + 1] = at;
   }
   bc.mark("bucket counts");
-  const uint64_t nsuf = bstart[NB];
-  if (nsuf + nseq != tlen) { g_err = "internal: suffix count"; return KAIJU_GPU_ERR_ARG; }
-  RawArr<I> SA(nsuf);
+  if (bstart[NB] != nsuf) { g_err = "internal: suffix count"; return KAIJU_GPU_ERR_ARG; }
   // positions enter their bucket in increasing order (needed for the terminator tie rule): the pieces of the text are the
   // ones of the counting pass, piece t fills its own share of every bucket
   parallel_chunks(nt, tlen, [&](uint64_t b, uint64_t e, unsigned t) {
@@ -328,6 +305,77 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
     for (auto &x : th) x.join();
   }
   bc.mark("suffix sort");
+  return KAIJU_GPU_OK;
+}
+
+#ifdef KAIJU_MKFMI_GPU
+// on the device (sufsort.hip): 32-bit positions, widened here for the 64-bit instantiation
+template <class I>
+int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, int device_id, RawArr<I> &SA, BuildClock &bc) {
+  uint64_t n = 0;
+  int rc;
+  kaiju_sufsort_stats st;
+  if (sizeof(I) == 4) {
+    rc = kj_sufsort_device(T.data(), tlen, device_id, reinterpret_cast<uint32_t *>(SA.data()), &n, &st, g_err);
+  } else {
+    RawArr<uint32_t> sa32(nsuf);
+    rc = kj_sufsort_device(T.data(), tlen, device_id, sa32.data(), &n, &st, g_err);
+    if (rc == KAIJU_GPU_OK && n == nsuf) for (uint64_t k = 0; k < nsuf; k++) SA[k] = (I)sa32[k];
+  }
+  if (rc != KAIJU_GPU_OK) return rc;
+  if (n != nsuf) { g_err = "internal: suffix count"; return KAIJU_GPU_ERR_ARG; }
+  bc.mark("suffix sort");
+  if (bc.on) {                                   // what the mark is made of: upload + rounds + download by HIP events, active suffixes per round
+    fprintf(stderr, "[kaiju mkfmi]   on device %d: %.1f ms, %u rounds, active", device_id, st.ms_sort, st.rounds);
+    for (uint32_t r = 0; r < st.rounds && r < KAIJU_SUFSORT_STATS_ROUNDS; r++) fprintf(stderr, " %llu", (unsigned long long)st.active[r]);
+    fprintf(stderr, "\n");
+  }
+  return KAIJU_GPU_OK;
+}
+#endif
+
+// copies > 1: the index of the database in which every sequence of the FASTA file occurs `copies` times in a row (copy t of
+// sequence i is sequence i * copies + t of that database) - WITHOUT sorting it again: equal suffixes of different sequences
+// compare by file order, so row r of the index of the file becomes the rows r * copies .. r * copies + copies - 1.  The output
+// is byte for byte what this builder (and the reference's) writes for the FASTA with the repeats spelled out
+// (tests/test_mkfmi_pin.py); a 2^32-row index for the tests of the wide path takes half a minute this way instead of the
+// seven minutes of sorting 4.3 G suffixes.  copy_taxids (optional): copy t of a sequence named X_<id> is named
+// X_<copy_taxids[(i + t) % n]>, so that the copies do not all carry one taxon.
+template <class I>
+int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t copies = 1, const uint64_t *copy_taxids = nullptr,
+          uint32_t n_copy_taxids = 0, int device_id = -1) {
+  // alphabet of kaiju-makedb:373 with the terminator in front (mkbwt.c:read_alphabet)
+  const char alphabet[] = "*ACDEFGHIKLMNPQRSTVWY";
+  const int alen = 21;
+  signed char trans[128];
+  trans[0] = 0;
+  for (int i = 1; i < 128; i++) trans[i] = isalpha(i) ? (signed char)(alen - 1) : (signed char)-1;
+  for (int i = 0; i < alen; i++) { trans[toupper(alphabet[i])] = (signed char)i; trans[tolower(alphabet[i])] = (signed char)i; }
+  // the reference's table maps the terminator character itself ('*') to code 0, i.e. a '*' inside
+  // the FASTA would plant a terminator in the middle of a sequence; it is skipped here
+  trans[(int)'*'] = -1;
+  std::vector<Seq> seqs;
+  RawArr<uint8_t> T;
+  BuildClock bc;
+  const unsigned nt = (unsigned)std::max(1, threads);
+  uint64_t tlen = 0;                              // == bwtlen of the file's own index
+  if (!read_fasta(faa, trans, nt, seqs, T, tlen)) return KAIJU_GPU_ERR_IO;
+  const uint64_t nseq = seqs.size();
+  bc.mark("read FASTA");
+  if (sizeof(I) == 4 && tlen >= 0xfffffff0ull) { g_err = "internal: index type too small"; return KAIJU_GPU_ERR_ARG; }
+
+  // ---- the suffix array of the letter suffixes (device_id >= 0: sorted on that GPU, libkaiju_mkfmi_gpu.so only) ---------------
+  const uint64_t nsuf = tlen - nseq;
+  RawArr<I> SA(nsuf);
+  {
+    int rc;
+#ifdef KAIJU_MKFMI_GPU
+    if (device_id >= 0) rc = sort_suffixes_device<I>(T, tlen, nsuf, device_id, SA, bc);
+    else
+#endif
+      rc = sort_suffixes_host<I>(T, tlen, nsuf, nt, SA, bc);
+    if (rc != KAIJU_GPU_OK) return rc;
+  }
 
   // ---- BWT of the file's own index: rows 0 .. nseq-1 are the terminator suffixes in file order, then the sorted suffixes;
   //      a terminator in front of a suffix says that it is a whole sequence --------------------------------------------
@@ -557,32 +605,58 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
 
 }  // namespace
 
-extern "C" int kaiju_build_fmi(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp) {
-  if (!faa_path || !out_fmi_path || chpt_exp < 0 || chpt_exp > 20) return KAIJU_GPU_ERR_ARG;
+namespace {
+// 32-bit suffix positions suffice below 4 G symbols; the 64-bit instantiation covers the rest
+// (KAIJU_MKFMI_FORCE64=1: the 64-bit instantiation on a small file - tests/test_mkfmi_pin.py)
+// (replicated: the FILE is sorted, so 32-bit suffix positions do as long as it has fewer than 4 G symbols)
+int build_any(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies, const uint64_t *copy_taxids,
+              uint32_t n_copy_taxids, int device_id) {
+  if (!faa_path || !out_fmi_path || chpt_exp < 0 || chpt_exp > 20 || copies < 1 || (n_copy_taxids && !copy_taxids)) return KAIJU_GPU_ERR_ARG;
   if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-  // 32-bit suffix positions suffice below 4 G symbols; the 64-bit instantiation covers the rest
   FILE *fp = fopen(faa_path, "rb");
   if (!fp) { g_err = std::string("cannot open ") + faa_path; return KAIJU_GPU_ERR_IO; }
   fseeko(fp, 0, SEEK_END);
   const off_t sz = ftello(fp);
   fclose(fp);
-  // (KAIJU_MKFMI_FORCE64=1: the 64-bit instantiation on a small file - tests/test_mkfmi_pin.py)
-  if ((uint64_t)sz < 0xf0000000ull && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp);
-  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp);
+  const bool narrow = (uint64_t)sz < 0xf0000000ull;
+  if (device_id >= 0 && !narrow) {
+    g_err = "suffix sort on the device: 32-bit positions only (file of " + std::to_string((uint64_t)sz) + " bytes); kaiju_build_fmi, the host builder, sorts with 64-bit positions";
+    return KAIJU_GPU_ERR_ARG;
+  }
+  if (narrow && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
+  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
+}
+}  // namespace
+
+extern "C" int kaiju_build_fmi(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp) {
+  return build_any(faa_path, out_fmi_path, threads, chpt_exp, 1, nullptr, 0, -1);
 }
 
 extern "C" int kaiju_build_fmi_replicated(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
                                           const uint64_t *copy_taxids, uint32_t n_copy_taxids) {
-  if (!faa_path || !out_fmi_path || chpt_exp < 0 || chpt_exp > 20 || copies < 1 || (n_copy_taxids && !copy_taxids)) return KAIJU_GPU_ERR_ARG;
-  if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-  // (the FILE is sorted, so 32-bit suffix positions do as long as it has fewer than 4 G symbols)
-  FILE *fp = fopen(faa_path, "rb");
-  if (!fp) { g_err = std::string("cannot open ") + faa_path; return KAIJU_GPU_ERR_IO; }
-  fseeko(fp, 0, SEEK_END);
-  const off_t sz = ftello(fp);
-  fclose(fp);
-  if ((uint64_t)sz < 0xf0000000ull && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids);
-  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids);
+  return build_any(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, -1);
 }
+
+#ifdef KAIJU_MKFMI_GPU
+extern "C" int kaiju_build_fmi_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, int device_id) {
+  const int rc = kj_sufsort_check_device(device_id, g_err);
+  return rc != KAIJU_GPU_OK ? rc : build_any(faa_path, out_fmi_path, threads, chpt_exp, 1, nullptr, 0, device_id);
+}
+
+extern "C" int kaiju_build_fmi_replicated_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
+                                                 const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id) {
+  const int rc = kj_sufsort_check_device(device_id, g_err);
+  return rc != KAIJU_GPU_OK ? rc : build_any(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
+}
+
+extern "C" int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats) {
+  if (text && ss_tlen_ok(tlen)) {           // (a refused length is refused before the text is looked at)
+    uint8_t top = 0;
+    for (uint64_t p = 0; p < tlen; p++) top = std::max(top, text[p]);
+    if (top > 20) { g_err = "suffix sort on the device: symbol codes are 0 .. 20"; return KAIJU_GPU_ERR_ARG; }
+  }
+  return kj_sufsort_device(text, tlen, device_id, sa_out, n_out, stats, g_err);
+}
+#endif
 
 extern "C" const char *kaiju_build_fmi_error(void) { return g_err.c_str(); }

@@ -5,6 +5,12 @@
  * bench.py and the tests need a way to make the indexes they classify on: this builder writes byte-identical files
  * (tests/test_mkfmi_pin.py).  It is compiled into a library of its own, kaiju_amd/libkaiju_mkfmi.so (host only, no HIP);
  * libkaiju_gpu.so does not contain it.
+ *
+ * A third library, kaiju_amd/libkaiju_mkfmi_gpu.so, is the same builder compiled with -DKAIJU_MKFMI_GPU plus sufsort.hip: it
+ * has every entry point of the host library and the *_device ones below, which sort the suffixes on a GPU (kj_sufsort.h) and
+ * leave everything else - BWT, sequence ranks, SA samples, byte coding, checkpoints, the file - to the same host code, so the
+ * file is byte for byte the host builder's (tests/test_gpu_sufsort.py).  The host library does not have the *_device entry
+ * points and needs no HIP runtime.
  */
 #ifndef KAIJU_MKFMI_H
 #define KAIJU_MKFMI_H
@@ -15,9 +21,10 @@
 extern "C" {
 #endif
 
-/* status codes: the values of include/kaiju_gpu.h's enum (0 ok, -1 bad argument, -2 file error) */
+/* status codes: the values of include/kaiju_gpu.h's enum (0 ok, -1 bad argument, -2 file error; the device entry points also
+   -4 no HIP device, -5 a HIP call failed, -6 not enough free device memory) */
 #ifndef KAIJU_GPU_H
-enum { KAIJU_GPU_OK = 0, KAIJU_GPU_ERR_ARG = -1, KAIJU_GPU_ERR_IO = -2 };
+enum { KAIJU_GPU_OK = 0, KAIJU_GPU_ERR_ARG = -1, KAIJU_GPU_ERR_IO = -2, KAIJU_GPU_ERR_NO_DEVICE = -4, KAIJU_GPU_ERR_HIP = -5, KAIJU_GPU_ERR_NOMEM = -6 };
 #endif
 
 /* Protein FASTA -> .fmi, format-compatible with the reference's kaiju-mkbwt (-a
@@ -33,6 +40,28 @@ int kaiju_build_fmi(const char *faa_path, const char *out_fmi_path, int threads,
 int kaiju_build_fmi_replicated(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
                                const uint64_t *copy_taxids, uint32_t n_copy_taxids);
 const char *kaiju_build_fmi_error(void);
+
+/* ---- libkaiju_mkfmi_gpu.so only: the suffix sort on the device ------------------------------------------------------------ */
+enum { KAIJU_SUFSORT_STATS_ROUNDS = 16 };
+typedef struct kaiju_sufsort_stats {
+  uint32_t rounds;                                 /* round 1 (keys of 12 symbols) and the doubling rounds; 0 without a suffix */
+  uint32_t reserved;
+  uint64_t active[KAIJU_SUFSORT_STATS_ROUNDS];     /* suffixes not yet final in front of round 1, 2, ...: active[0] = all */
+  float ms_sort;                                   /* HIP events around upload, sort and download */
+  float reserved2;
+} kaiju_sufsort_stats;
+/* kaiju_build_fmi / kaiju_build_fmi_replicated with the suffixes sorted on device `device_id`; the same bytes.  32-bit positions
+   only: a file of 0xf0000000 bytes and more is KAIJU_GPU_ERR_ARG (kaiju_build_fmi, the host builder, has the 64-bit sort); under
+   KAIJU_MKFMI_FORCE64 the device sorts in 32 bits and the builder widens the result.  A device_id that does not exist:
+   KAIJU_GPU_ERR_ARG.  The sort's scratch (about 33 bytes per symbol, kj_sufsort.h: ss_scratch_bytes) is compared with the free
+   device memory before anything is allocated: KAIJU_GPU_ERR_NOMEM. */
+int kaiju_build_fmi_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, int device_id);
+int kaiju_build_fmi_replicated_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
+                                      const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id);
+/* The sorter alone.  Host pointers, blocking: text up, positions down.  text[0, tlen): codes 0 .. 20, the last one 0;
+   sa_out: room for tlen minus the number of terminators; *n_out: how many were written.  tlen >= 0xf0000000 is refused
+   (KAIJU_GPU_ERR_ARG) before the text is looked at.  stats may be NULL. */
+int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats);
 
 #ifdef __cplusplus
 }
