@@ -47,32 +47,19 @@
 #include "kj_format_verbose.h"
 #include "kj_format_seq.h"
 #include "kj_format_names.h"
+#include "kj_lines.h"
 // Libraries linked from a source list of their own (the compile-time variants of tests/tools/mem_variants.sh: search lanes
-// only) need not hold ingest.hip: the two functions are weak references here, and without them the entry points below say
-// KAIJU_GPU_ERR_UNSUPPORTED.  kaiju_amd/build.py always links ingest.hip.
+// only) need not hold ingest.hip, format.hip, format_verbose.hip with accessions.cpp, format_seq.hip or format_names.hip: their
+// functions are weak references here, and without them the entry points below say KAIJU_GPU_ERR_UNSUPPORTED.
+// kaiju_amd/build.py always links them all.
 __attribute__((weak)) decltype(kj_ingest_launch) kj_ingest_launch;
-__attribute__((weak)) decltype(kj_ingest_free) kj_ingest_free;
-// (format.hip likewise)
 __attribute__((weak)) decltype(kj_format_launch) kj_format_launch;
-__attribute__((weak)) decltype(kj_format_written) kj_format_written;
-__attribute__((weak)) decltype(kj_format_free) kj_format_free;
-// (format_verbose.hip and accessions.cpp likewise)
 __attribute__((weak)) decltype(kj_fv_lengths) kj_fv_lengths;
-__attribute__((weak)) decltype(kj_fv_total) kj_fv_total;
 __attribute__((weak)) decltype(kj_fv_write) kj_fv_write;
-__attribute__((weak)) decltype(kj_fv_written) kj_fv_written;
-__attribute__((weak)) decltype(kj_fv_free) kj_fv_free;
 extern "C" __attribute__((weak)) decltype(kaiju_accession_ranks) kaiju_accession_ranks;
-// (format_seq.hip likewise)
 __attribute__((weak)) decltype(kj_fs_lengths) kj_fs_lengths;
-__attribute__((weak)) decltype(kj_fs_total) kj_fs_total;
 __attribute__((weak)) decltype(kj_fs_write) kj_fs_write;
-__attribute__((weak)) decltype(kj_fs_written) kj_fs_written;
-__attribute__((weak)) decltype(kj_fs_free) kj_fs_free;
-// (format_names.hip likewise)
 __attribute__((weak)) decltype(kj_fn_launch) kj_fn_launch;
-__attribute__((weak)) decltype(kj_fn_written) kj_fn_written;
-__attribute__((weak)) decltype(kj_fn_free) kj_fn_free;
 __attribute__((weak)) decltype(kj_fn_device) kj_fn_device;
 extern "C" __attribute__((weak)) decltype(kaiju_gpu_taxon_names_max_annotation) kaiju_gpu_taxon_names_max_annotation;
 #ifdef KJ_GREEDY3                    // the experimental row-pool Greedy lane: variant builds only
@@ -2053,27 +2040,24 @@ struct kaiju_gpu_ctx {
   std::vector<uint8_t> vb_host;      // ... and where it arrives
   std::vector<uint32_t> vb_h_nacc, vb_h_acc;   // (host side of the accessions: kept, so that a call does not fault 80 bytes per read in again)
   DevBuf h_seqs, h_off, h_hits;      // staging for the host-buffer entry point
-  kj_ingest_scratch *ingest = nullptr;                 // record extraction (ingest.hip): line tables, flags, scan partials
+  kjl::Scratch ingest;                                 // record extraction (ingest.hip): line tables, flags, scan partials
   DevBuf ing_text1, ing_text2, ing_names, ing_info;    // ... and the staging of its host-pointer entry points
-  kj_format_scratch *format = nullptr;                 // the output lines (format.hip): line lengths and offsets, decisions
+  kjl::Lines format;                                   // the output lines (format.hip): line lengths and offsets, decisions
   DevBuf fmt_pw, fmt_out, fmt_info;                    // ... the table of its E-value gate, the staging of its host-pointer entry points
   bool fmt_pw_ok = false;                              // (kjf::build_pow_table's verdict)
-  kj_fv_scratch *format_v = nullptr;                   // the lines of -v (format_verbose.hip): lengths, offsets, the shadow
-  DevBuf fv_out, fv_info, fv_trunc, fv_total;          // ... and the staging of its host-pointer entry points
-  kj_fs_scratch *format_s = nullptr;                   // the lines of kaijux / kaijup (format_seq.hip); staged in fv_out / fv_info / fv_trunc
-  kj_fn_scratch *format_n = nullptr;                   // the lines with taxon names (format_names.hip); staged in fmt_out / fmt_info
+  kjl::Lines format_v;                                 // the lines of -v (format_verbose.hip): lengths, offsets, the shadow
+  DevBuf fv_out, fv_info, fv_trunc;                    // ... and the staging of its host-pointer entry points
+  kjl::Lines format_s;                                 // the lines of kaijux / kaijup (format_seq.hip); staged in fv_out / fv_info / fv_trunc
+  kjl::Lines format_n;                                 // the lines with taxon names (format_names.hip); staged in fmt_out / fmt_info
   kaiju_gpu_stats stats{};
   uint32_t last_n = 0;
   uint32_t max_read_len = 1024;
   ~kaiju_gpu_ctx() {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
-    if (ingest) kj_ingest_free(ingest);
-    if (format && kj_format_free) kj_format_free(format);
-    if (format_v && kj_fv_free) kj_fv_free(format_v);
-    if (format_s && kj_fs_free) kj_fs_free(format_s);
-    if (format_n && kj_fn_free) kj_fn_free(format_n);
-    DevBuf *all[] = {&fv_out, &fv_info, &fv_trunc, &fv_total, &fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
+    ingest.release();
+    for (kjl::Lines *l : {&format, &format_v, &format_s, &format_n}) l->release();
+    DevBuf *all[] = {&fv_out, &fv_info, &fv_trunc, &fmt_pw, &fmt_out, &fmt_info, &ing_text1, &ing_text2, &ing_names, &ing_info, &pep, &frags, &meta, &counters, &retry_list, &seg_items, &seg_recs, &h_seqs, &h_off, &h_hits, &h_compact, &seglist, &loc_list, &todo_list,
                      &vb_nacc, &vb_acc, &vb_tlen, &vb_text, &vb_bestv, &vb_bestv_retry, &vb_packed, &vb_pos,
                      &redo_bitmap, &redo_list, &redo_items, &redo_index, &redo_pool, &redo_work, &redo_cls};
     for (DevBuf *b : all) if (b->p) (void)hipFree(b->p);
@@ -2915,7 +2899,7 @@ extern "C" int kaiju_gpu_parse_block_device(kaiju_gpu_ctx *ctx, const void *d_te
   if (!ctx) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
   KJ_HIP(hipSetDevice(ctx->ix->device));
   const char *err = "";
-  const int rc = kj_ingest_launch(&ctx->ingest, stream ? static_cast<hipStream_t>(stream) : ctx->stream, d_text1, bytes1, d_text2, bytes2,
+  const int rc = kj_ingest_launch(ctx->ingest, stream ? static_cast<hipStream_t>(stream) : ctx->stream, d_text1, bytes1, d_text2, bytes2,
                                   fastq, keep_names, rec_cap, d_seqs, d_off, d_names, d_info, &err);
   return rc ? fail(rc, err) : KAIJU_GPU_OK;
   });
@@ -2940,7 +2924,7 @@ static int parse_host_text(kaiju_gpu_ctx *ctx, const char *text1, uint64_t bytes
   if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
   if (bytes2) KJ_HIP(hipMemcpyAsync(ctx->ing_text2.p, text2, bytes2, hipMemcpyHostToDevice, s));
   const char *err = "";
-  rc = kj_ingest_launch(&ctx->ingest, s, ctx->ing_text1.p, bytes1, text2 ? ctx->ing_text2.p : nullptr, bytes2, fastq, keep_names, rec_cap,
+  rc = kj_ingest_launch(ctx->ingest, s, ctx->ing_text1.p, bytes1, text2 ? ctx->ing_text2.p : nullptr, bytes2, fastq, keep_names, rec_cap,
                         ctx->h_seqs.p, static_cast<uint64_t *>(ctx->h_off.p), static_cast<kaiju_gpu_name_span *>(ctx->ing_names.p),
                         static_cast<kaiju_gpu_parse_info *>(ctx->ing_info.p), &err);
   if (rc) return fail(rc, err);
@@ -2969,6 +2953,23 @@ extern "C" int kaiju_gpu_parse_block(kaiju_gpu_ctx *ctx, const char *text1, uint
   });
 }
 
+// text in, the records parsed and classified on the device (blocks for the parse's counts only): *n records of paired or
+// single reads, their 16-byte records in ctx->h_compact, offsets in h_off, name spans in ing_names, text 1 in ing_text1
+static int classify_text_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1, const char *text2,
+                                uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap, kaiju_gpu_parse_info *info, uint32_t *n, bool *paired) {
+  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info)) return rc;
+  if (info->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
+  *paired = text2 != nullptr;
+  *n = reads_emitted(*info, *paired, rec_cap);
+  int rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)*n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if (*n == 0) return KAIJU_GPU_OK;
+  if ((rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info->max_mate_len)))) return rc;
+  if ((rc = ensure(ctx->h_hits, (size_t)*n * sizeof(kaiju_gpu_hit)))) return rc;
+  return kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), *n, *paired ? 1 : 0,
+                                                 static_cast<kaiju_gpu_hit *>(ctx->h_hits.p), static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), ctx->stream);
+}
+
 extern "C" int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_taxonomy *t, const char *text1, uint64_t bytes1,
                                                const char *text2, uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap,
                                                kaiju_gpu_compact *out, uint64_t *off, kaiju_gpu_name_span *names,
@@ -2977,22 +2978,15 @@ extern "C" int kaiju_gpu_classify_text_compact(kaiju_gpu_ctx *ctx, const kaiju_g
   if (int rc = no_device()) return rc;
   if (!ctx || !t || !off || (!names && rec_cap) || (!out && rec_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
   if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
-  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info)) return rc;
-  if (info->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
-  const bool paired = text2 != nullptr;
-  const uint32_t n = reads_emitted(*info, paired, rec_cap);
+  uint32_t n;
+  bool paired;
+  if (int rc = classify_text_device(ctx, t, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info, &n, &paired)) return rc;
   hipStream_t s = ctx->stream;
   KJ_HIP(hipMemcpyAsync(off, ctx->h_off.p, (2 * (size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (n == 0) { KJ_HIP(hipStreamSynchronize(s)); return KAIJU_GPU_OK; }
-  KJ_HIP(hipMemcpyAsync(names, ctx->ing_names.p, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyDeviceToHost, s));
-  int rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info->max_mate_len));
-  if (rc) return rc;
-  if ((rc = ensure(ctx->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
-  if ((rc = ensure(ctx->h_compact, (size_t)n * sizeof(kaiju_gpu_compact)))) return rc;
-  rc = kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), n, paired ? 1 : 0,
-                                               static_cast<kaiju_gpu_hit *>(ctx->h_hits.p), static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), s);
-  if (rc) return rc;
-  KJ_HIP(hipMemcpyAsync(out, ctx->h_compact.p, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyDeviceToHost, s));
+  if (n) {
+    KJ_HIP(hipMemcpyAsync(names, ctx->ing_names.p, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyDeviceToHost, s));
+    KJ_HIP(hipMemcpyAsync(out, ctx->h_compact.p, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyDeviceToHost, s));
+  }
   KJ_HIP(hipStreamSynchronize(s));
   return KAIJU_GPU_OK;
   });
@@ -3004,21 +2998,27 @@ static int no_format() {
   return KAIJU_GPU_OK;
 }
 extern "C" uint64_t kaiju_gpu_format_bound(uint64_t bytes1, uint32_t n) { return bytes1 + (uint64_t)kjf::kLineExtra * n; }
-// the passes on stream s; all pointers device pointers
-static int format_launch(kaiju_gpu_ctx *ctx, hipStream_t s, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
-                         const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
-                         kaiju_gpu_format_info *d_info) {
-  if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup are not made on the device");
+// what every formatter takes from the context: the checks they share (behind the caller's own of the index's id_mode, whose
+// wording differs), and the parameters of the decision
+static int format_params(const kaiju_gpu_ctx *ctx, int paired, kjf::Params &P) {
   if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
   if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
-  kjf::Params P{};
   P.db_length = ctx->ix->info.db_length;
   P.min_evalue = ctx->params.min_evalue;
   P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
   P.protein = ctx->params.input_is_protein ? 1 : 0;
   P.paired = paired ? 1 : 0;
+  return KAIJU_GPU_OK;
+}
+// the passes on stream s; all pointers device pointers
+static int format_launch(kaiju_gpu_ctx *ctx, hipStream_t s, const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, int paired,
+                         const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap,
+                         kaiju_gpu_format_info *d_info) {
+  if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup are not made on the device");
+  kjf::Params P{};
+  if (int rc = format_params(ctx, paired, P)) return rc;
   const char *err = "";
-  const int rc = kj_format_launch(&ctx->format, s, P, static_cast<const double *>(ctx->fmt_pw.p), d_recs, d_off, n, d_text1, bytes1, d_names,
+  const int rc = kj_format_launch(ctx->format, s, P, static_cast<const double *>(ctx->fmt_pw.p), d_recs, d_off, n, d_text1, bytes1, d_names,
                                   d_out, out_cap, d_info, &err);
   return rc ? fail(rc, err) : KAIJU_GPU_OK;
 }
@@ -3036,15 +3036,44 @@ extern "C" int kaiju_gpu_format_compact_device(kaiju_gpu_ctx *ctx, const kaiju_g
   });
 }
 
-// *info and the bytes the passes wrote, from ctx->fmt_info / fmt_out to the host; blocks
-static int format_download(kaiju_gpu_ctx *ctx, hipStream_t s, char *out, uint64_t out_cap, kaiju_gpu_format_info *info) {
-  KJ_HIP(hipMemcpyAsync(info, ctx->fmt_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
+// *info (one of the three kaiju_gpu_format_*_info) from d_info and the bytes the passes of st wrote from d_out to the host; blocks
+template <class Info>
+static int format_download(hipStream_t s, const kjl::Lines &st, const DevBuf &d_info, const DevBuf &d_out, char *out, uint64_t out_cap, Info *info) {
+  KJ_HIP(hipMemcpyAsync(info, d_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));
   uint64_t written = info->text_bytes;
-  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_format_written(ctx->format), sizeof written, hipMemcpyDeviceToHost));
+  if (info->overflow) KJ_HIP(hipMemcpy(&written, st.written, sizeof written, hipMemcpyDeviceToHost));
   if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
-  if (written) KJ_HIP(hipMemcpy(out, ctx->fmt_out.p, written, hipMemcpyDeviceToHost));
+  if (written) KJ_HIP(hipMemcpy(out, d_out.p, written, hipMemcpyDeviceToHost));
   return KAIJU_GPU_OK;
+}
+
+// the inputs of the three-column lines (with or without names) from the host to ctx->ing_text1 / h_compact / h_off /
+// ing_names, and room for the output in fmt_out / fmt_info
+static int format_stage(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, const char *text1, uint64_t bytes1,
+                        const kaiju_gpu_name_span *names, uint64_t out_cap, size_t info_bytes) {
+  int rc;
+  if ((rc = ensure(ctx->ing_text1, bytes1 + 64))) return rc;
+  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
+  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
+  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
+  if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
+  if ((rc = ensure(ctx->fmt_info, info_bytes))) return rc;
+  hipStream_t s = ctx->stream;
+  if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
+  if (n) {
+    KJ_HIP(hipMemcpyAsync(ctx->h_compact.p, recs, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
+  }
+  return KAIJU_GPU_OK;
+}
+// format_launch on what format_stage / classify_text_device left in the context, then the download
+static int format_staged(kaiju_gpu_ctx *ctx, uint32_t n, int paired, uint64_t bytes1, char *out, uint64_t out_cap, kaiju_gpu_format_info *info) {
+  const int rc = format_launch(ctx, ctx->stream, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p),
+                               n, paired, ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), ctx->fmt_out.p,
+                               out_cap, static_cast<kaiju_gpu_format_info *>(ctx->fmt_info.p));
+  return rc ? rc : format_download(ctx->stream, ctx->format, ctx->fmt_info, ctx->fmt_out, out, out_cap, info);
 }
 
 extern "C" int kaiju_gpu_format_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, int paired,
@@ -3056,25 +3085,8 @@ extern "C" int kaiju_gpu_format_compact(kaiju_gpu_ctx *ctx, const kaiju_gpu_comp
   if (!ctx || !info || (n && (!recs || !off || !names)) || (!text1 && bytes1) || (!out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
   if (bytes1 > kjf::kMaxBytes || n > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes, a batch below 2^31 records");
   KJ_HIP(hipSetDevice(ctx->ix->device));
-  int rc;
-  if ((rc = ensure(ctx->ing_text1, bytes1 + 64))) return rc;
-  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
-  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
-  if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
-  if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_info)))) return rc;
-  hipStream_t s = ctx->stream;
-  if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
-  if (n) {
-    KJ_HIP(hipMemcpyAsync(ctx->h_compact.p, recs, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyHostToDevice, s));
-    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
-  }
-  rc = format_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired,
-                     ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), ctx->fmt_out.p, out_cap,
-                     static_cast<kaiju_gpu_format_info *>(ctx->fmt_info.p));
-  if (rc) return rc;
-  return format_download(ctx, s, out, out_cap, info);
+  if (int rc = format_stage(ctx, recs, off, n, text1, bytes1, names, out_cap, sizeof(kaiju_gpu_format_info))) return rc;
+  return format_staged(ctx, n, paired, bytes1, out, out_cap, info);
   });
 }
 
@@ -3089,28 +3101,13 @@ extern "C" int kaiju_gpu_classify_text_to_text(kaiju_gpu_ctx *ctx, const kaiju_g
   if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
   if (bytes1 > kjf::kMaxBytes) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes");
   memset(info_format, 0, sizeof *info_format);
-  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info_parse)) return rc;
-  if (info_parse->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
-  const bool paired = text2 != nullptr;
-  const uint32_t n = reads_emitted(*info_parse, paired, rec_cap);
-  hipStream_t s = ctx->stream;
+  uint32_t n;
+  bool paired;
   int rc;
+  if ((rc = classify_text_device(ctx, t, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info_parse, &n, &paired))) return rc;
   if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
   if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_info)))) return rc;
-  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
-  if (n) {
-    if ((rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info_parse->max_mate_len)))) return rc;
-    if ((rc = ensure(ctx->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
-    rc = kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info_parse->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), n,
-                                                 paired ? 1 : 0, static_cast<kaiju_gpu_hit *>(ctx->h_hits.p),
-                                                 static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), s);
-    if (rc) return rc;
-  }
-  rc = format_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired ? 1 : 0,
-                     ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), ctx->fmt_out.p, out_cap,
-                     static_cast<kaiju_gpu_format_info *>(ctx->fmt_info.p));
-  if (rc) return rc;
-  if ((rc = format_download(ctx, s, out_text, out_cap, info_format))) return rc;
+  if ((rc = format_staged(ctx, n, paired ? 1 : 0, bytes1, out_text, out_cap, info_format))) return rc;
   if (info_format->overflow) return fail(KAIJU_GPU_ERR_ARG, "the output text needs more than out_cap bytes");
   return KAIJU_GPU_OK;
   });
@@ -3132,16 +3129,10 @@ static int format_names_launch(kaiju_gpu_ctx *ctx, hipStream_t s, const kaiju_gp
   if (!names) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
   if (kj_fn_device(names) != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "the taxon names live on another device");
   if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup carry no taxon");
-  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
-  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
   kjf::Params P{};
-  P.db_length = ctx->ix->info.db_length;
-  P.min_evalue = ctx->params.min_evalue;
-  P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
-  P.protein = ctx->params.input_is_protein ? 1 : 0;
-  P.paired = paired ? 1 : 0;
+  if (int rc = format_params(ctx, paired, P)) return rc;
   const char *err = "";
-  const int rc = kj_fn_launch(&ctx->format_n, s, P, static_cast<const double *>(ctx->fmt_pw.p), d_recs, d_off, n, d_text1, bytes1, d_names, names, drop,
+  const int rc = kj_fn_launch(ctx->format_n, s, P, static_cast<const double *>(ctx->fmt_pw.p), d_recs, d_off, n, d_text1, bytes1, d_names, names, drop,
                               d_out, out_cap, d_info, &err);
   return rc ? fail(rc, err) : KAIJU_GPU_OK;
 }
@@ -3160,15 +3151,13 @@ extern "C" int kaiju_gpu_format_names_device(kaiju_gpu_ctx *ctx, const kaiju_gpu
   });
 }
 
-// *info and the bytes the passes wrote, from ctx->fmt_info / fmt_out to the host; blocks
-static int format_names_download(kaiju_gpu_ctx *ctx, hipStream_t s, char *out, uint64_t out_cap, kaiju_gpu_format_names_info *info) {
-  KJ_HIP(hipMemcpyAsync(info, ctx->fmt_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
-  KJ_HIP(hipStreamSynchronize(s));
-  uint64_t written = info->text_bytes;
-  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fn_written(ctx->format_n), sizeof written, hipMemcpyDeviceToHost));
-  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
-  if (written) KJ_HIP(hipMemcpy(out, ctx->fmt_out.p, written, hipMemcpyDeviceToHost));
-  return KAIJU_GPU_OK;
+// format_names_launch on what format_stage / classify_text_device left in the context, then the download
+static int format_names_staged(kaiju_gpu_ctx *ctx, uint32_t n, int paired, uint64_t bytes1, const kaiju_gpu_taxon_names *names, int drop, char *out,
+                               uint64_t out_cap, kaiju_gpu_format_names_info *info) {
+  const int rc = format_names_launch(ctx, ctx->stream, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p),
+                                     n, paired, ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), names, drop,
+                                     ctx->fmt_out.p, out_cap, static_cast<kaiju_gpu_format_names_info *>(ctx->fmt_info.p));
+  return rc ? rc : format_download(ctx->stream, ctx->format_n, ctx->fmt_info, ctx->fmt_out, out, out_cap, info);
 }
 
 extern "C" int kaiju_gpu_format_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_compact *recs, const uint64_t *off, uint32_t n, int paired,
@@ -3181,25 +3170,8 @@ extern "C" int kaiju_gpu_format_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_compac
   if (!ctx || !info || !names || (n && (!recs || !off || !names_spans)) || (!text1 && bytes1) || (!out && out_cap)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
   if (bytes1 > kjf::kMaxBytes || n > kjf::kMaxRecords) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes, a batch below 2^31 records");
   KJ_HIP(hipSetDevice(ctx->ix->device));
-  int rc;
-  if ((rc = ensure(ctx->ing_text1, bytes1 + 64))) return rc;
-  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
-  if ((rc = ensure(ctx->h_off, (2 * (size_t)n + 1) * 8))) return rc;
-  if ((rc = ensure(ctx->ing_names, ((size_t)n + 1) * sizeof(kaiju_gpu_name_span)))) return rc;
-  if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
-  if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_names_info)))) return rc;
-  hipStream_t s = ctx->stream;
-  if (bytes1) KJ_HIP(hipMemcpyAsync(ctx->ing_text1.p, text1, bytes1, hipMemcpyHostToDevice, s));
-  if (n) {
-    KJ_HIP(hipMemcpyAsync(ctx->h_compact.p, recs, (size_t)n * sizeof(kaiju_gpu_compact), hipMemcpyHostToDevice, s));
-    KJ_HIP(hipMemcpyAsync(ctx->h_off.p, off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-    KJ_HIP(hipMemcpyAsync(ctx->ing_names.p, names_spans, (size_t)n * sizeof(kaiju_gpu_name_span), hipMemcpyHostToDevice, s));
-  }
-  rc = format_names_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired,
-                           ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), names, drop_unclassified,
-                           ctx->fmt_out.p, out_cap, static_cast<kaiju_gpu_format_names_info *>(ctx->fmt_info.p));
-  if (rc) return rc;
-  return format_names_download(ctx, s, out, out_cap, info);
+  if (int rc = format_stage(ctx, recs, off, n, text1, bytes1, names_spans, out_cap, sizeof(kaiju_gpu_format_names_info))) return rc;
+  return format_names_staged(ctx, n, paired, bytes1, names, drop_unclassified, out, out_cap, info);
   });
 }
 
@@ -3214,28 +3186,13 @@ extern "C" int kaiju_gpu_classify_text_to_text_names(kaiju_gpu_ctx *ctx, const k
   if (t->device != ctx->ix->device) return fail(KAIJU_GPU_ERR_ARG, "taxonomy lives on another device");
   if (bytes1 > kjf::kMaxBytes) return fail(KAIJU_GPU_ERR_ARG, "a block of text must be below 2^32 - 32 bytes");
   memset(info_format, 0, sizeof *info_format);
-  if (int rc = parse_host_text(ctx, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info_parse)) return rc;
-  if (info_parse->overflow) return fail(KAIJU_GPU_ERR_ARG, "the text holds more records than rec_cap");
-  const bool paired = text2 != nullptr;
-  const uint32_t n = reads_emitted(*info_parse, paired, rec_cap);
-  hipStream_t s = ctx->stream;
+  uint32_t n;
+  bool paired;
   int rc;
+  if ((rc = classify_text_device(ctx, t, text1, bytes1, text2, bytes2, fastq, keep_names, rec_cap, info_parse, &n, &paired))) return rc;
   if ((rc = ensure(ctx->fmt_out, out_cap + 64))) return rc;
   if ((rc = ensure(ctx->fmt_info, sizeof(kaiju_gpu_format_names_info)))) return rc;
-  if ((rc = ensure(ctx->h_compact, ((size_t)n + 1) * sizeof(kaiju_gpu_compact)))) return rc;
-  if (n) {
-    if ((rc = kaiju_gpu_set_max_read_length(ctx, std::max(1u, info_parse->max_mate_len)))) return rc;
-    if ((rc = ensure(ctx->h_hits, (size_t)n * sizeof(kaiju_gpu_hit)))) return rc;
-    rc = kaiju_gpu_classify_batch_device_compact(ctx, t, ctx->h_seqs.p, info_parse->seq_bytes, static_cast<const uint64_t *>(ctx->h_off.p), n,
-                                                 paired ? 1 : 0, static_cast<kaiju_gpu_hit *>(ctx->h_hits.p),
-                                                 static_cast<kaiju_gpu_compact *>(ctx->h_compact.p), s);
-    if (rc) return rc;
-  }
-  rc = format_names_launch(ctx, s, static_cast<const kaiju_gpu_compact *>(ctx->h_compact.p), static_cast<const uint64_t *>(ctx->h_off.p), n, paired ? 1 : 0,
-                           ctx->ing_text1.p, bytes1, static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p), names, drop_unclassified,
-                           ctx->fmt_out.p, out_cap, static_cast<kaiju_gpu_format_names_info *>(ctx->fmt_info.p));
-  if (rc) return rc;
-  if ((rc = format_names_download(ctx, s, out_text, out_cap, info_format))) return rc;
+  if ((rc = format_names_staged(ctx, n, paired ? 1 : 0, bytes1, names, drop_unclassified, out_text, out_cap, info_format))) return rc;
   if (info_format->overflow) return fail(KAIJU_GPU_ERR_ARG, "the output text needs more than out_cap bytes");
   return KAIJU_GPU_OK;
   });
@@ -3299,19 +3256,13 @@ extern "C" uint64_t kaiju_gpu_index_accession_bytes(const kaiju_gpu_index *ix) {
 // the inputs of the passes that come from the context and its index; everything else is the caller's
 static int fv_job(kaiju_gpu_ctx *ctx, int paired, kjv::Job &J) {
   if (ctx->ix->id_mode != KAIJU_GPU_IDS_TAXON) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the lines of kaijux / kaijup are not made on the device");
-  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
-  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
+  if (int rc = format_params(ctx, paired, J.P)) return rc;
   {
     std::lock_guard<std::mutex> lk(g_acc_mutex);
     if (!ctx->ix->acc_ready) return fail(KAIJU_GPU_ERR_ARG, "the index has no accession table on the device: call kaiju_gpu_index_upload_accessions() first");
     J.acc_blob = ctx->ix->acc_blob; J.acc_off = ctx->ix->acc_off; J.acc_len = ctx->ix->acc_len; J.acc_rank = ctx->ix->acc_rank;
   }
   J.nseq = (uint32_t)ctx->ix->names.size();
-  J.P.db_length = ctx->ix->info.db_length;
-  J.P.min_evalue = ctx->params.min_evalue;
-  J.P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
-  J.P.protein = ctx->params.input_is_protein ? 1 : 0;
-  J.P.paired = paired ? 1 : 0;
   J.pw = static_cast<const double *>(ctx->fmt_pw.p);
   return KAIJU_GPU_OK;
 }
@@ -3335,22 +3286,11 @@ extern "C" int kaiju_gpu_format_verbose_device(kaiju_gpu_ctx *ctx, const kaiju_g
   J.names_bytes = names_bytes; J.names = d_names;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   const char *err = "";
-  int rc = kj_fv_lengths(&ctx->format_v, s, J, n, &err);
+  int rc = kj_fv_lengths(ctx->format_v, s, J, n, &err);
   if (rc) return fail(rc, err);
-  rc = kj_fv_write(ctx->format_v, s, d_out, out_cap, d_info, &err);
+  rc = kj_fv_write(ctx->format_v, s, J, n, d_out, out_cap, d_info, &err);
   return rc ? fail(rc, err) : KAIJU_GPU_OK;
   });
-}
-
-// *info and the bytes the passes wrote, from ctx->fv_info / fv_out to the host; blocks
-static int fv_download(kaiju_gpu_ctx *ctx, hipStream_t s, char *out, uint64_t out_cap, kaiju_gpu_format_verbose_info *info) {
-  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
-  KJ_HIP(hipStreamSynchronize(s));
-  uint64_t written = info->text_bytes;
-  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fv_written(ctx->format_v), sizeof written, hipMemcpyDeviceToHost));
-  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
-  if (written) KJ_HIP(hipMemcpy(out, ctx->fv_out.p, written, hipMemcpyDeviceToHost));
-  return KAIJU_GPU_OK;
 }
 
 extern "C" int kaiju_gpu_format_verbose(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hits, const kaiju_gpu_verbose *vout, const uint64_t *text_pos,
@@ -3412,11 +3352,11 @@ extern "C" int kaiju_gpu_format_verbose(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit 
   J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
   J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
   const char *err = "";
-  rc = kj_fv_lengths(&ctx->format_v, s, J, n, &err);
-  if (rc == 0) rc = kj_fv_write(ctx->format_v, s, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
+  rc = kj_fv_lengths(ctx->format_v, s, J, n, &err);
+  if (rc == 0) rc = kj_fv_write(ctx->format_v, s, J, n, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
   // (the host arrays above are pageable: the copies have left them when hipMemcpyAsync returns)
   if (rc) { (void)hipStreamSynchronize(s); return fail(rc, err); }
-  return fv_download(ctx, s, out, out_cap, info);
+  return format_download(s, ctx->format_v, ctx->fv_info, ctx->fv_out, out, out_cap, info);
   });
 }
 
@@ -3456,17 +3396,17 @@ extern "C" int kaiju_gpu_classify_batch_verbose_text(kaiju_gpu_ctx *ctx, const k
   J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
   J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
   const char *err = "";
-  if ((rc = kj_fv_lengths(&ctx->format_v, s, J, n_reads, &err))) return fail(rc, err);
+  if ((rc = kj_fv_lengths(ctx->format_v, s, J, n_reads, &err))) return fail(rc, err);
   // the one wait inside: the size of the text, so that the output can be sized
   uint64_t total = 0;
-  KJ_HIP(hipMemcpyAsync(&total, kj_fv_total(ctx->format_v), sizeof total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipMemcpyAsync(&total, ctx->format_v.total, sizeof total, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));
   call_mark("verbose text: size of the text on the host");
   // (a line is its name and at most: "C\t" "\t" two numbers, 21 ids, 20 prefixes, the peptides, the tabs)
   if (total > names_bytes + (uint64_t)n_reads * (512 + 20ull * (kjv::kMaxPrefix + 1) + ctx->vb_text_cap)) return fail(KAIJU_GPU_ERR_HIP, "the format passes report an impossible size");
   if ((rc = ensure(ctx->fv_out, total + 64))) return rc;
   if (ctx->vb_host.size() < total) ctx->vb_host.resize((size_t)total);
-  if ((rc = kj_fv_write(ctx->format_v, s, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
+  if ((rc = kj_fv_write(ctx->format_v, s, J, n_reads, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
   KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
   if (total) KJ_HIP(hipMemcpyAsync(ctx->vb_host.data(), ctx->fv_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));
@@ -3536,19 +3476,13 @@ extern "C" uint64_t kaiju_gpu_index_seq_name_bytes(const kaiju_gpu_index *ix) {
 static int fs_job(kaiju_gpu_ctx *ctx, int paired, int u_rule, kjq::Job &J) {
   if (ctx->ix->id_mode != KAIJU_GPU_IDS_SEQUENCE) return fail(KAIJU_GPU_ERR_ARG, "the lines of kaijux / kaijup need an index loaded with KAIJU_GPU_IDS_SEQUENCE");
   if (u_rule != KAIJU_GPU_U_RULE_NUCLEOTIDE && u_rule != KAIJU_GPU_U_RULE_PROTEIN) return fail(KAIJU_GPU_ERR_ARG, "u_rule must be KAIJU_GPU_U_RULE_NUCLEOTIDE or KAIJU_GPU_U_RULE_PROTEIN");
-  if (paired && ctx->params.input_is_protein) return fail(KAIJU_GPU_ERR_ARG, "protein reads have no mates");
-  if (!ctx->fmt_pw_ok) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "a score beyond the table of the E-value gate has a factor other than +0.0");
+  if (int rc = format_params(ctx, paired, J.P)) return rc;
   {
     std::lock_guard<std::mutex> lk(g_sn_mutex);
     if (!ctx->ix->sn_ready) return fail(KAIJU_GPU_ERR_ARG, "the index has no sequence-name table on the device: call kaiju_gpu_index_upload_seq_names() first");
     J.sn_blob = ctx->ix->sn_blob; J.sn_off = ctx->ix->sn_off; J.sn_len = ctx->ix->sn_len;
   }
   J.nseq = (uint32_t)ctx->ix->names.size();
-  J.P.db_length = ctx->ix->info.db_length;
-  J.P.min_evalue = ctx->params.min_evalue;
-  J.P.gate = ctx->params.mode == 1 && ctx->params.use_evalue ? 1 : 0;
-  J.P.protein = ctx->params.input_is_protein ? 1 : 0;
-  J.P.paired = paired ? 1 : 0;
   J.pw = static_cast<const double *>(ctx->fmt_pw.p);
   J.u_rule = (uint32_t)u_rule;
   J.min_frag = ctx->params.min_fragment_length;
@@ -3576,9 +3510,9 @@ extern "C" int kaiju_gpu_format_seq_device(kaiju_gpu_ctx *ctx, const kaiju_gpu_h
   J.names_text = static_cast<const uint8_t *>(d_names_text); J.names_bytes = names_bytes; J.names = d_names;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   const char *err = "";
-  int rc = kj_fs_lengths(&ctx->format_s, s, J, n, &err);
+  int rc = kj_fs_lengths(ctx->format_s, s, J, n, &err);
   if (rc) return fail(rc, err);
-  rc = kj_fs_write(ctx->format_s, s, d_out, out_cap, d_info, &err);
+  rc = kj_fs_write(ctx->format_s, s, J, n, d_out, out_cap, d_info, &err);
   return rc ? fail(rc, err) : KAIJU_GPU_OK;
   });
 }
@@ -3648,17 +3582,11 @@ extern "C" int kaiju_gpu_format_seq(kaiju_gpu_ctx *ctx, const kaiju_gpu_hit *hit
   J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
   J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
   const char *err = "";
-  rc = kj_fs_lengths(&ctx->format_s, s, J, n, &err);
-  if (rc == 0) rc = kj_fs_write(ctx->format_s, s, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
+  rc = kj_fs_lengths(ctx->format_s, s, J, n, &err);
+  if (rc == 0) rc = kj_fs_write(ctx->format_s, s, J, n, ctx->fv_out.p, out_cap, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err);
   // (the host arrays above are pageable: the copies have left them when hipMemcpyAsync returns)
   if (rc) { (void)hipStreamSynchronize(s); return fail(rc, err); }
-  KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
-  KJ_HIP(hipStreamSynchronize(s));
-  uint64_t written = info->text_bytes;
-  if (info->overflow) KJ_HIP(hipMemcpy(&written, kj_fs_written(ctx->format_s), sizeof written, hipMemcpyDeviceToHost));
-  if (written > out_cap) return fail(KAIJU_GPU_ERR_HIP, "the format passes report more bytes than the capacity");
-  if (written) KJ_HIP(hipMemcpy(out, ctx->fv_out.p, written, hipMemcpyDeviceToHost));
-  return KAIJU_GPU_OK;
+  return format_download(s, ctx->format_s, ctx->fv_info, ctx->fv_out, out, out_cap, info);
   });
 }
 
@@ -3696,10 +3624,10 @@ extern "C" int kaiju_gpu_classify_batch_seq_text(kaiju_gpu_ctx *ctx, const char 
   J.names_text = static_cast<const uint8_t *>(ctx->ing_text1.p); J.names_bytes = names_bytes;
   J.names = static_cast<const kaiju_gpu_name_span *>(ctx->ing_names.p);
   const char *err = "";
-  if ((rc = kj_fs_lengths(&ctx->format_s, s, J, n_reads, &err))) return fail(rc, err);
+  if ((rc = kj_fs_lengths(ctx->format_s, s, J, n_reads, &err))) return fail(rc, err);
   // the one wait inside: the size of the text, so that the output can be sized
   uint64_t total = 0;
-  KJ_HIP(hipMemcpyAsync(&total, kj_fs_total(ctx->format_s), sizeof total, hipMemcpyDeviceToHost, s));
+  KJ_HIP(hipMemcpyAsync(&total, ctx->format_s.total, sizeof total, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));
   call_mark("seq text: size of the text on the host");
   // (a line is its name and at most: "C\t" "\t" a number, 21 names with their commas, the peptides, two tabs, "\n")
@@ -3707,7 +3635,7 @@ extern "C" int kaiju_gpu_classify_batch_seq_text(kaiju_gpu_ctx *ctx, const char 
     return fail(KAIJU_GPU_ERR_HIP, "the format passes report an impossible size");
   if ((rc = ensure(ctx->fv_out, total + 64))) return rc;
   if (ctx->vb_host.size() < total) ctx->vb_host.resize((size_t)total);
-  if ((rc = kj_fs_write(ctx->format_s, s, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
+  if ((rc = kj_fs_write(ctx->format_s, s, J, n_reads, ctx->fv_out.p, total, static_cast<kaiju_gpu_format_verbose_info *>(ctx->fv_info.p), &err))) return fail(rc, err);
   KJ_HIP(hipMemcpyAsync(info, ctx->fv_info.p, sizeof *info, hipMemcpyDeviceToHost, s));
   if (total) KJ_HIP(hipMemcpyAsync(ctx->vb_host.data(), ctx->fv_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
   KJ_HIP(hipStreamSynchronize(s));

@@ -6,22 +6,19 @@
 //                       sequence names by shuffles inside the team (registers only), for kaijup the fragment scan of the reads
 //                       the decision left unclassified (a segmented scan over the team per 32 letters), the length of the
 //                       line; counts of 'C' lines, inexact and truncated records
-//   k_fs_off_sums / k_fs_off_top / k_fs_off_apply   line_off[] = prefix sum of the lengths (64 bit)
+//   kjl::k_scan_sums / k_scan_top / k_scan_apply <FsCount>   line_off[] = prefix sum of the lengths (64 bit; kj_lines.h)
 //   k_fs_mid            best and the ids column of every 'C' line that fits, by the record's team, into the shadow of the output
-//   k_fs_write          per lane 16 aligned bytes of the output
+//   k_fs_write          per lane 16 aligned bytes of the output: kjl::write_blocks over format_schunk
 //   k_fs_finish         kaiju_gpu_format_verbose_info, by one lane with ordinary stores
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "../../include/kaiju_gpu.h"
 #include "kj_format_seq.h"
-#include "kj_scan.h"
+#include "kj_lines.h"
 
 using namespace kjq;
-using kjs::OpAdd64;
-using kjs::block_scan_excl;
 
 namespace {
 
@@ -59,6 +56,8 @@ __device__ bool team_has_fragment(const Job &J, uint32_t r, uint32_t i, uint64_t
   for (int d = 1; d < (int)kTeam; d <<= 1) hit |= (uint32_t)__shfl_xor((int)hit, d, (int)kTeam);
   return hit != 0;
 }
+
+struct FsCount { const Hdr *hdr; __device__ uint64_t operator()() const { return hdr->n; } };   // elements of the scan
 
 __global__ void k_fs_init(Hdr *h, uint32_t n) {
   if (blockIdx.x || threadIdx.x) return;
@@ -103,39 +102,6 @@ __global__ __launch_bounds__(kFsBlock) void k_fs_len(Job J, uint32_t n) {
   }
 }
 
-__global__ __launch_bounds__(kFsBlock) void k_fs_off_sums(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    block_scan_excl<uint64_t>(i < M ? J.llen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (threadIdx.x == 0) J.oblk[b] = tot;
-  }
-}
-
-__global__ __launch_bounds__(kFsBlock) void k_fs_off_top(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  uint64_t carry = 0;
-  for (uint64_t i0 = 0; i0 < nb; i0 += kFsBlock) {
-    const uint64_t i = i0 + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < nb ? J.oblk[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < nb) J.oblk_base[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) J.line_off[M] = carry;
-}
-
-__global__ __launch_bounds__(kFsBlock) void k_fs_off_apply(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < M ? J.llen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < M) J.line_off[i] = J.oblk_base[b] + ex;
-  }
-}
-
 __global__ __launch_bounds__(kFsBlock) void k_fs_mid(Job J) {
   const uint32_t n = J.hdr->n;
   const uint32_t i = threadIdx.x & (kTeam - 1);
@@ -152,27 +118,8 @@ __global__ __launch_bounds__(kFsBlock) void k_fs_mid(Job J) {
 }
 
 __global__ __launch_bounds__(kFsBlock) void k_fs_write(Job J) {
-  __shared__ uint32_t s_lo, s_hi;
-  const uint32_t n = J.hdr->n;
-  const uint64_t total = J.line_off[n];
-  const uint64_t lim = total < J.out_cap ? total : J.out_cap;          // no line reaches beyond it
-  const uint64_t nb = (lim + kBlockBytes - 1) / kBlockBytes;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    if (threadIdx.x == 0) {
-      uint32_t lo, hi;
-      kjf::block_records(J.line_off, n, b, lim, &lo, &hi);
-      s_lo = lo; s_hi = hi;
-    }
-    __syncthreads();
-    const uint32_t lo = s_lo, hi = s_hi;
-    const uint64_t c = b * kBlockLanes + threadIdx.x;
-    if (c * kChunk < lim) {
-      Chunk v;
-      const uint32_t m = format_schunk(J, c, lo, hi, total, &v);
-      if (m) kjf::store_chunk(J.out, c, v, m);
-    }
-    __syncthreads();
-  }
+  kjl::write_blocks(J.line_off, J.hdr->n, J.out, J.out_cap,
+                    [&](uint64_t c, uint32_t lo, uint32_t hi, uint64_t total, Chunk *v) { return format_schunk(J, c, lo, hi, total, v); });
 }
 
 __global__ void k_fs_finish(Job J) {
@@ -182,40 +129,8 @@ __global__ void k_fs_finish(Job J) {
   *J.info = kjv::make_info(J.line_off[n], *J.hdr, J.out_cap);
 }
 
-}  // namespace
-
 // ---- host side: scratch and the queue of passes ----------------------------------------------------------------------
-struct kj_fs_scratch {
-  void *p = nullptr;
-  size_t cap = 0;
-  void *shadow = nullptr;
-  size_t shadow_cap = 0;
-  Job job{};                    // of the last kj_fs_lengths
-  uint32_t n = 0;
-  bool have = false;
-};
-
-void kj_fs_free(kj_fs_scratch *s) {
-  if (!s) return;
-  if (s->p) (void)hipFree(s->p);
-  if (s->shadow) (void)hipFree(s->shadow);
-  delete s;
-}
-const uint64_t *kj_fs_total(const kj_fs_scratch *s) { return s && s->have ? s->job.line_off + s->n : nullptr; }
-const uint64_t *kj_fs_written(const kj_fs_scratch *s) { return s && s->have ? &s->job.hdr->written : nullptr; }
-
-namespace {
-struct Carver {
-  uint8_t *base;
-  size_t at = 0;
-  template <class T> T *take(size_t n) {
-    at = (at + 255) & ~(size_t)255;
-    T *q = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += n * sizeof(T);
-    return q;
-  }
-};
-void carve(Carver &c, Job &J, uint32_t n) {
+void carve(kjl::Carver &c, Job &J, uint32_t n) {
   const size_t nblk = (size_t)n / kScanBlock + 2;
   J.llen = c.take<uint64_t>((size_t)n + 1);
   J.line_off = c.take<uint64_t>((size_t)n + 1);
@@ -226,59 +141,41 @@ void carve(Carver &c, Job &J, uint32_t n) {
 }
 }  // namespace
 
-int kj_fs_lengths(kj_fs_scratch **scratch, hipStream_t s, const Job &in, uint32_t n, const char **err) {
+int kj_fs_lengths(kjl::Lines &st, hipStream_t s, Job &J, uint32_t n, const char **err) {
   *err = "";
-  if (!scratch || !in.pw || (n && (!in.hits || !in.off || !in.names)) || (!in.names_text && in.names_bytes) ||
-      (n && in.pep && (!in.text_pos || !in.text_len)) || (n && in.u_rule == KAIJU_GPU_U_RULE_PROTEIN && !in.seqs)) {
+  if (!J.pw || (n && (!J.hits || !J.off || !J.names)) || (!J.names_text && J.names_bytes) ||
+      (n && J.pep && (!J.text_pos || !J.text_len)) || (n && J.u_rule == KAIJU_GPU_U_RULE_PROTEIN && !J.seqs)) {
     *err = "NULL argument";
     return KAIJU_GPU_ERR_ARG;
   }
-  if (in.u_rule != KAIJU_GPU_U_RULE_NUCLEOTIDE && in.u_rule != KAIJU_GPU_U_RULE_PROTEIN) { *err = "u_rule must be KAIJU_GPU_U_RULE_NUCLEOTIDE or _PROTEIN"; return KAIJU_GPU_ERR_ARG; }
-  if (in.names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) { *err = "the names must be below 2^32 - 32 bytes, a batch below 2^31 records"; return KAIJU_GPU_ERR_ARG; }
-  if (!in.sn_blob || !in.sn_len || !in.sn_off) { *err = "no sequence-name table"; return KAIJU_GPU_ERR_ARG; }
-  Job J = in;
+  if (J.u_rule != KAIJU_GPU_U_RULE_NUCLEOTIDE && J.u_rule != KAIJU_GPU_U_RULE_PROTEIN) { *err = "u_rule must be KAIJU_GPU_U_RULE_NUCLEOTIDE or _PROTEIN"; return KAIJU_GPU_ERR_ARG; }
+  if (J.names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) { *err = "the names must be below 2^32 - 32 bytes, a batch below 2^31 records"; return KAIJU_GPU_ERR_ARG; }
+  if (!J.sn_blob || !J.sn_len || !J.sn_off) { *err = "no sequence-name table"; return KAIJU_GPU_ERR_ARG; }
   J.out = nullptr; J.out_cap = 0; J.info = nullptr; J.shadow = nullptr;
-  Carver measure{nullptr};
+  kjl::Carver measure{nullptr};
   carve(measure, J, n);
-  if (!*scratch) { *scratch = new (std::nothrow) kj_fs_scratch(); if (!*scratch) { *err = "out of host memory"; return KAIJU_GPU_ERR_NOMEM; } }
-  kj_fs_scratch *sc = *scratch;
-  sc->have = false;
-  if (measure.at + 256 > sc->cap) {
-    // (the passes of an earlier call on another stream may still use the old scratch)
-    if (sc->p) { if (hipDeviceSynchronize() != hipSuccess || hipFree(sc->p) != hipSuccess) { *err = "hipFree"; return KAIJU_GPU_ERR_HIP; } sc->p = nullptr; sc->cap = 0; }
-    const size_t want = measure.at + measure.at / 8 + 256;
-    if (hipMalloc(&sc->p, want) != hipSuccess) { (void)hipGetLastError(); *err = "hipMalloc of the sequence format scratch"; return KAIJU_GPU_ERR_NOMEM; }
-    sc->cap = want;
-  }
-  Carver c{static_cast<uint8_t *>(sc->p)};
+  if (int rc = st.mem.reserve(measure.at, 256, "hipMalloc of the sequence format scratch", err)) return rc;
+  kjl::Carver c{static_cast<uint8_t *>(st.mem.p)};
   carve(c, J, n);
-  sc->job = J; sc->n = n; sc->have = true;
+  st.total = J.line_off + n;
+  st.written = &J.hdr->written;
 
   const dim3 blk(kFsBlock);
   const dim3 tgrid((unsigned)std::min<uint64_t>(8192, (uint64_t)n / kTeamsPerBlock + 1));
   const dim3 ogrid((unsigned)std::min<uint64_t>(2048, (uint64_t)n / kScanBlock + 1));
   hipLaunchKernelGGL(k_fs_init, dim3(1), dim3(64), 0, s, J.hdr, n);
   hipLaunchKernelGGL(k_fs_len, tgrid, blk, 0, s, J, n);
-  hipLaunchKernelGGL(k_fs_off_sums, ogrid, blk, 0, s, J);
-  hipLaunchKernelGGL(k_fs_off_top, dim3(1), blk, 0, s, J);
-  hipLaunchKernelGGL(k_fs_off_apply, ogrid, blk, 0, s, J);
+  kjl::launch_offsets(s, ogrid, FsCount{J.hdr}, J.llen, J.oblk, J.oblk_base, J.line_off);
   if (hipGetLastError() != hipSuccess) { *err = "a kernel of the sequence format passes could not be launched"; return KAIJU_GPU_ERR_HIP; }
   return KAIJU_GPU_OK;
 }
 
-int kj_fs_write(kj_fs_scratch *sc, hipStream_t s, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err) {
+int kj_fs_write(kjl::Lines &st, hipStream_t s, Job &J, uint32_t n, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err) {
   *err = "";
-  if (!sc || !sc->have || !d_info || (!d_out && out_cap)) { *err = "NULL argument"; return KAIJU_GPU_ERR_ARG; }
+  if (!J.hdr || !d_info || (!d_out && out_cap)) { *err = "NULL argument"; return KAIJU_GPU_ERR_ARG; }
   if ((uintptr_t)d_out & (kChunk - 1)) { *err = "the output pointer must be 16-byte aligned"; return KAIJU_GPU_ERR_ARG; }
-  if (out_cap + 64 > sc->shadow_cap) {
-    if (sc->shadow) { if (hipDeviceSynchronize() != hipSuccess || hipFree(sc->shadow) != hipSuccess) { *err = "hipFree"; return KAIJU_GPU_ERR_HIP; } sc->shadow = nullptr; sc->shadow_cap = 0; }
-    const size_t want = out_cap + out_cap / 8 + 256;
-    if (hipMalloc(&sc->shadow, want) != hipSuccess) { (void)hipGetLastError(); *err = "hipMalloc of the shadow of the output (out_cap bytes)"; return KAIJU_GPU_ERR_NOMEM; }
-    sc->shadow_cap = want;
-  }
-  Job &J = sc->job;
-  J.out = static_cast<uint8_t *>(d_out); J.out_cap = out_cap; J.info = d_info; J.shadow = static_cast<uint8_t *>(sc->shadow);
-  const uint32_t n = sc->n;
+  if (int rc = st.shadow.reserve(out_cap, 64, "hipMalloc of the shadow of the output (out_cap bytes)", err)) return rc;
+  J.out = static_cast<uint8_t *>(d_out); J.out_cap = out_cap; J.info = d_info; J.shadow = static_cast<uint8_t *>(st.shadow.p);
   const dim3 blk(kFsBlock);
   const dim3 tgrid((unsigned)std::min<uint64_t>(8192, (uint64_t)n / kTeamsPerBlock + 1));
   const dim3 wgrid((unsigned)std::min<uint64_t>(8192, out_cap / kBlockBytes + 1));

@@ -5,22 +5,19 @@
 //   k_fv_len            a team of 32 lanes per record, two records per wavefront: the decision, the sorted places of ids and
 //                       accession ranks by shuffles inside the team (registers only), the length of the line; counts of 'C'
 //                       lines, inexact and truncated records
-//   k_fv_off_sums / k_fv_off_top / k_fv_off_apply   line_off[] = prefix sum of the lengths (64 bit)
+//   kjl::k_scan_sums / k_scan_top / k_scan_apply <FvCount>   line_off[] = prefix sum of the lengths (64 bit; kj_lines.h)
 //   k_fv_mid            columns 3 to 6 of every 'C' line that fits, by the record's team, into the shadow of the output
-//   k_fv_write          per lane 16 aligned bytes of the output
+//   k_fv_write          per lane 16 aligned bytes of the output: kjl::write_blocks over format_vchunk
 //   k_fv_finish         kaiju_gpu_format_verbose_info, by one lane with ordinary stores
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "../../include/kaiju_gpu.h"
 #include "kj_format_verbose.h"
-#include "kj_scan.h"
+#include "kj_lines.h"
 
 using namespace kjv;
-using kjs::OpAdd64;
-using kjs::block_scan_excl;
 
 namespace {
 
@@ -36,6 +33,8 @@ struct TeamShfl {
   __device__ uint32_t rank(uint32_t mine, uint32_t k) const { return (uint32_t)__shfl((int)mine, (int)k, (int)kTeam); }
   __device__ uint32_t klen(uint32_t mine, uint32_t k) const { return (uint32_t)__shfl((int)mine, (int)k, (int)kTeam); }
 };
+
+struct FvCount { const Hdr *hdr; __device__ uint64_t operator()() const { return hdr->n; } };   // elements of the scan
 
 __global__ void k_fv_init(Hdr *h, uint32_t n) {
   if (blockIdx.x || threadIdx.x) return;
@@ -75,39 +74,6 @@ __global__ __launch_bounds__(kFvBlock) void k_fv_len(Job J, uint32_t n) {
   }
 }
 
-__global__ __launch_bounds__(kFvBlock) void k_fv_off_sums(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    block_scan_excl<uint64_t>(i < M ? J.llen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (threadIdx.x == 0) J.oblk[b] = tot;
-  }
-}
-
-__global__ __launch_bounds__(kFvBlock) void k_fv_off_top(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  uint64_t carry = 0;
-  for (uint64_t i0 = 0; i0 < nb; i0 += kFvBlock) {
-    const uint64_t i = i0 + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < nb ? J.oblk[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < nb) J.oblk_base[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) J.line_off[M] = carry;
-}
-
-__global__ __launch_bounds__(kFvBlock) void k_fv_off_apply(Job J) {
-  const uint64_t M = J.hdr->n, nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < M ? J.llen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < M) J.line_off[i] = J.oblk_base[b] + ex;
-  }
-}
-
 __global__ __launch_bounds__(kFvBlock) void k_fv_mid(Job J) {
   const uint32_t n = J.hdr->n;
   const uint32_t i = threadIdx.x & (kTeam - 1);
@@ -125,27 +91,8 @@ __global__ __launch_bounds__(kFvBlock) void k_fv_mid(Job J) {
 }
 
 __global__ __launch_bounds__(kFvBlock) void k_fv_write(Job J) {
-  __shared__ uint32_t s_lo, s_hi;
-  const uint32_t n = J.hdr->n;
-  const uint64_t total = J.line_off[n];
-  const uint64_t lim = total < J.out_cap ? total : J.out_cap;          // no line reaches beyond it
-  const uint64_t nb = (lim + kBlockBytes - 1) / kBlockBytes;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    if (threadIdx.x == 0) {
-      uint32_t lo, hi;
-      kjf::block_records(J.line_off, n, b, lim, &lo, &hi);
-      s_lo = lo; s_hi = hi;
-    }
-    __syncthreads();
-    const uint32_t lo = s_lo, hi = s_hi;
-    const uint64_t c = b * kBlockLanes + threadIdx.x;
-    if (c * kChunk < lim) {
-      Chunk v;
-      const uint32_t m = format_vchunk(J, c, lo, hi, total, &v);
-      if (m) kjf::store_chunk(J.out, c, v, m);
-    }
-    __syncthreads();
-  }
+  kjl::write_blocks(J.line_off, J.hdr->n, J.out, J.out_cap,
+                    [&](uint64_t c, uint32_t lo, uint32_t hi, uint64_t total, Chunk *v) { return format_vchunk(J, c, lo, hi, total, v); });
 }
 
 __global__ void k_fv_finish(Job J) {
@@ -155,40 +102,8 @@ __global__ void k_fv_finish(Job J) {
   *J.info = make_info(J.line_off[n], *J.hdr, J.out_cap);
 }
 
-}  // namespace
-
 // ---- host side: scratch and the queue of passes ----------------------------------------------------------------------
-struct kj_fv_scratch {
-  void *p = nullptr;
-  size_t cap = 0;
-  void *shadow = nullptr;
-  size_t shadow_cap = 0;
-  Job job{};                    // of the last kj_fv_lengths
-  uint32_t n = 0;
-  bool have = false;
-};
-
-void kj_fv_free(kj_fv_scratch *s) {
-  if (!s) return;
-  if (s->p) (void)hipFree(s->p);
-  if (s->shadow) (void)hipFree(s->shadow);
-  delete s;
-}
-const uint64_t *kj_fv_total(const kj_fv_scratch *s) { return s && s->have ? s->job.line_off + s->n : nullptr; }
-const uint64_t *kj_fv_written(const kj_fv_scratch *s) { return s && s->have ? &s->job.hdr->written : nullptr; }
-
-namespace {
-struct Carver {
-  uint8_t *base;
-  size_t at = 0;
-  template <class T> T *take(size_t n) {
-    at = (at + 255) & ~(size_t)255;
-    T *q = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += n * sizeof(T);
-    return q;
-  }
-};
-void carve(Carver &c, Job &J, uint32_t n) {
+void carve(kjl::Carver &c, Job &J, uint32_t n) {
   const size_t nblk = (size_t)n / kScanBlock + 2;
   J.llen = c.take<uint64_t>((size_t)n + 1);
   J.line_off = c.take<uint64_t>((size_t)n + 1);
@@ -199,58 +114,40 @@ void carve(Carver &c, Job &J, uint32_t n) {
 }
 }  // namespace
 
-int kj_fv_lengths(kj_fv_scratch **scratch, hipStream_t s, const Job &in, uint32_t n, const char **err) {
+int kj_fv_lengths(kjl::Lines &st, hipStream_t s, Job &J, uint32_t n, const char **err) {
   *err = "";
-  if (!scratch || !in.pw || (n && (!in.hits || !in.recs || !in.off || !in.names || !in.n_acc || !in.acc_iseq || !in.text_pos || !in.text_len)) ||
-      (!in.names_text && in.names_bytes)) {
+  if (!J.pw || (n && (!J.hits || !J.recs || !J.off || !J.names || !J.n_acc || !J.acc_iseq || !J.text_pos || !J.text_len)) ||
+      (!J.names_text && J.names_bytes)) {
     *err = "NULL argument";
     return KAIJU_GPU_ERR_ARG;
   }
-  if (in.names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) { *err = "the names must be below 2^32 - 32 bytes, a batch below 2^31 records"; return KAIJU_GPU_ERR_ARG; }
-  if (!in.acc_rank || !in.acc_len || !in.acc_off) { *err = "no accession table"; return KAIJU_GPU_ERR_ARG; }
-  Job J = in;
+  if (J.names_bytes > kjf::kMaxBytes || n > kjf::kMaxRecords) { *err = "the names must be below 2^32 - 32 bytes, a batch below 2^31 records"; return KAIJU_GPU_ERR_ARG; }
+  if (!J.acc_rank || !J.acc_len || !J.acc_off) { *err = "no accession table"; return KAIJU_GPU_ERR_ARG; }
   J.out = nullptr; J.out_cap = 0; J.info = nullptr; J.shadow = nullptr;
-  Carver measure{nullptr};
+  kjl::Carver measure{nullptr};
   carve(measure, J, n);
-  if (!*scratch) { *scratch = new (std::nothrow) kj_fv_scratch(); if (!*scratch) { *err = "out of host memory"; return KAIJU_GPU_ERR_NOMEM; } }
-  kj_fv_scratch *sc = *scratch;
-  sc->have = false;
-  if (measure.at + 256 > sc->cap) {
-    // (the passes of an earlier call on another stream may still use the old scratch)
-    if (sc->p) { if (hipDeviceSynchronize() != hipSuccess || hipFree(sc->p) != hipSuccess) { *err = "hipFree"; return KAIJU_GPU_ERR_HIP; } sc->p = nullptr; sc->cap = 0; }
-    const size_t want = measure.at + measure.at / 8 + 256;
-    if (hipMalloc(&sc->p, want) != hipSuccess) { (void)hipGetLastError(); *err = "hipMalloc of the verbose format scratch"; return KAIJU_GPU_ERR_NOMEM; }
-    sc->cap = want;
-  }
-  Carver c{static_cast<uint8_t *>(sc->p)};
+  if (int rc = st.mem.reserve(measure.at, 256, "hipMalloc of the verbose format scratch", err)) return rc;
+  kjl::Carver c{static_cast<uint8_t *>(st.mem.p)};
   carve(c, J, n);
-  sc->job = J; sc->n = n; sc->have = true;
+  st.total = J.line_off + n;
+  st.written = &J.hdr->written;
 
   const dim3 blk(kFvBlock);
   const dim3 tgrid((unsigned)std::min<uint64_t>(8192, (uint64_t)n / kTeamsPerBlock + 1));
   const dim3 ogrid((unsigned)std::min<uint64_t>(2048, (uint64_t)n / kScanBlock + 1));
   hipLaunchKernelGGL(k_fv_init, dim3(1), dim3(64), 0, s, J.hdr, n);
   hipLaunchKernelGGL(k_fv_len, tgrid, blk, 0, s, J, n);
-  hipLaunchKernelGGL(k_fv_off_sums, ogrid, blk, 0, s, J);
-  hipLaunchKernelGGL(k_fv_off_top, dim3(1), blk, 0, s, J);
-  hipLaunchKernelGGL(k_fv_off_apply, ogrid, blk, 0, s, J);
+  kjl::launch_offsets(s, ogrid, FvCount{J.hdr}, J.llen, J.oblk, J.oblk_base, J.line_off);
   if (hipGetLastError() != hipSuccess) { *err = "a kernel of the verbose format passes could not be launched"; return KAIJU_GPU_ERR_HIP; }
   return KAIJU_GPU_OK;
 }
 
-int kj_fv_write(kj_fv_scratch *sc, hipStream_t s, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err) {
+int kj_fv_write(kjl::Lines &st, hipStream_t s, Job &J, uint32_t n, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err) {
   *err = "";
-  if (!sc || !sc->have || !d_info || (!d_out && out_cap)) { *err = "NULL argument"; return KAIJU_GPU_ERR_ARG; }
+  if (!J.hdr || !d_info || (!d_out && out_cap)) { *err = "NULL argument"; return KAIJU_GPU_ERR_ARG; }
   if ((uintptr_t)d_out & (kChunk - 1)) { *err = "the output pointer must be 16-byte aligned"; return KAIJU_GPU_ERR_ARG; }
-  if (out_cap + 64 > sc->shadow_cap) {
-    if (sc->shadow) { if (hipDeviceSynchronize() != hipSuccess || hipFree(sc->shadow) != hipSuccess) { *err = "hipFree"; return KAIJU_GPU_ERR_HIP; } sc->shadow = nullptr; sc->shadow_cap = 0; }
-    const size_t want = out_cap + out_cap / 8 + 256;
-    if (hipMalloc(&sc->shadow, want) != hipSuccess) { (void)hipGetLastError(); *err = "hipMalloc of the shadow of the output (out_cap bytes)"; return KAIJU_GPU_ERR_NOMEM; }
-    sc->shadow_cap = want;
-  }
-  Job &J = sc->job;
-  J.out = static_cast<uint8_t *>(d_out); J.out_cap = out_cap; J.info = d_info; J.shadow = static_cast<uint8_t *>(sc->shadow);
-  const uint32_t n = sc->n;
+  if (int rc = st.shadow.reserve(out_cap, 64, "hipMalloc of the shadow of the output (out_cap bytes)", err)) return rc;
+  J.out = static_cast<uint8_t *>(d_out); J.out_cap = out_cap; J.info = d_info; J.shadow = static_cast<uint8_t *>(st.shadow.p);
   const dim3 blk(kFvBlock);
   const dim3 tgrid((unsigned)std::min<uint64_t>(8192, (uint64_t)n / kTeamsPerBlock + 1));
   const dim3 wgrid((unsigned)std::min<uint64_t>(8192, out_cap / kBlockBytes + 1));

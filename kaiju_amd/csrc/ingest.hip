@@ -11,22 +11,20 @@
 //   k_ing_fa_flag       FASTA: header flags
 //   k_ing_rec_scatter   rec_line[] from the prefix sum over the header flags
 //   k_ing_span_len      per record: letters of the span(s), the name, the name comparison of pairs, longest mate
-//   k_ing_off_sums / k_ing_off_top / k_ing_off_apply   off[] = prefix sum of the mate lengths (64 bit)
+//   kjl::k_scan_sums / k_scan_top / k_scan_apply <IngMates>   off[] = prefix sum of the mate lengths (64 bit; kj_lines.h)
 //   k_ing_span_copy     the letters to seqs + off[..]
 //   k_ing_finish        kaiju_gpu_parse_info, by one lane with ordinary stores
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "../../include/kaiju_gpu.h"
 #include "kj_ingest.h"
-#include "kj_scan.h"
+#include "kj_lines.h"
 
 using namespace kji;
 using kjs::OpAdd32;
-using kjs::OpAdd64;
-using kjs::block_scan_excl;     // (shared with format.hip)
+using kjs::block_scan_excl;
 
 namespace {
 
@@ -266,41 +264,11 @@ __global__ __launch_bounds__(kIngBlock) void k_ing_span_len(IngRec R) {
   if ((threadIdx.x & 63) == 0 && lmax) atomicMax(&R.sh->max_mate_len, lmax);
 }
 
-__global__ __launch_bounds__(kIngBlock) void k_ing_off_sums(IngRec R) {
-  uint32_t n1, n2;
-  const uint64_t M = 2 * (uint64_t)emitted(R, &n1, &n2), nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    block_scan_excl<uint64_t>(i < M ? R.mlen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (threadIdx.x == 0) R.oblk[b] = tot;
-  }
-}
-
-__global__ __launch_bounds__(kIngBlock) void k_ing_off_top(IngRec R) {
-  uint32_t n1, n2;
-  const uint64_t M = 2 * (uint64_t)emitted(R, &n1, &n2), nb = (M + kScanBlock - 1) / kScanBlock;
-  uint64_t carry = 0;
-  for (uint64_t i0 = 0; i0 < nb; i0 += kIngBlock) {
-    const uint64_t i = i0 + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < nb ? R.oblk[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < nb) R.oblk_base[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) R.off[M] = carry;
-}
-
-__global__ __launch_bounds__(kIngBlock) void k_ing_off_apply(IngRec R) {
-  uint32_t n1, n2;
-  const uint64_t M = 2 * (uint64_t)emitted(R, &n1, &n2), nb = (M + kScanBlock - 1) / kScanBlock;
-  for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const uint64_t i = b * kScanBlock + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl<uint64_t>(i < M ? R.mlen[i] : 0ull, 0ull, &tot, OpAdd64());
-    if (i < M) R.off[i] = R.oblk_base[b] + ex;
-  }
-}
+// elements of the scan that makes off[]: the mates of the records emitted
+struct IngMates {
+  IngRec R;
+  __device__ uint64_t operator()() const { uint32_t n1, n2; return 2 * (uint64_t)emitted(R, &n1, &n2); }
+};
 
 __device__ void team_copy_letters(const uint8_t *text, const Span &s, uint8_t *dst) {
   const uint64_t nc = span_chunks(s);
@@ -351,32 +319,8 @@ __global__ void k_ing_finish(IngRec R) {
   *R.info = o;
 }
 
-}  // namespace
-
 // ---- host side: scratch and the queue of passes ----------------------------------------------------------------------
-struct kj_ingest_scratch {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-
-void kj_ingest_free(kj_ingest_scratch *s) {
-  if (!s) return;
-  if (s->p) (void)hipFree(s->p);
-  delete s;
-}
-
-namespace {
-struct Carver {
-  uint8_t *base;
-  size_t at = 0;
-  template <class T> T *take(size_t n) {
-    at = (at + 255) & ~(size_t)255;
-    T *q = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += n * sizeof(T);
-    return q;
-  }
-};
-void carve_file(Carver &c, IngFile &f, const void *text, uint64_t bytes, uint32_t rec_cap) {
+void carve_file(kjl::Carver &c, IngFile &f, const void *text, uint64_t bytes, uint32_t rec_cap) {
   f.text = static_cast<const uint8_t *>(text);
   f.bytes = bytes;
   f.n_tiles = (uint32_t)((bytes + kTileBytes - 1) / kTileBytes);
@@ -390,7 +334,7 @@ void carve_file(Carver &c, IngFile &f, const void *text, uint64_t bytes, uint32_
   f.rec_line = c.take<uint32_t>((size_t)rec_cap + 1);
   f.hdr = c.take<IngHdr>(1);
 }
-void carve(Carver &c, IngRec &R, const void *t1, uint64_t b1, const void *t2, uint64_t b2, uint32_t rec_cap) {
+void carve(kjl::Carver &c, IngRec &R, const void *t1, uint64_t b1, const void *t2, uint64_t b2, uint32_t rec_cap) {
   carve_file(c, R.f1, t1, b1, rec_cap);
   carve_file(c, R.f2, t2, b2, rec_cap);
   const size_t nblk = (2 * (size_t)rec_cap) / kScanBlock + 2;
@@ -401,30 +345,22 @@ void carve(Carver &c, IngRec &R, const void *t1, uint64_t b1, const void *t2, ui
 }
 }  // namespace
 
-int kj_ingest_launch(kj_ingest_scratch **scratch, hipStream_t s, const void *d_text1, uint64_t bytes1, const void *d_text2,
+int kj_ingest_launch(kjl::Scratch &scratch, hipStream_t s, const void *d_text1, uint64_t bytes1, const void *d_text2,
                      uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap, void *d_seqs, uint64_t *d_off,
                      kaiju_gpu_name_span *d_names, kaiju_gpu_parse_info *d_info, const char **err) {
   *err = "";
   const bool paired = d_text2 != nullptr;
-  if (!scratch || !d_off || !d_info || (!d_text1 && bytes1) || (!paired && bytes2) || (rec_cap && !d_names) || (bytes1 + bytes2 && !d_seqs)) {
+  if (!d_off || !d_info || (!d_text1 && bytes1) || (!paired && bytes2) || (rec_cap && !d_names) || (bytes1 + bytes2 && !d_seqs)) {
     *err = "NULL argument";
     return KAIJU_GPU_ERR_ARG;
   }
   if (bytes1 > kMaxBytes || bytes2 > kMaxBytes || rec_cap > 0x7ffffff0u) { *err = "a block of text must be below 2^32 bytes"; return KAIJU_GPU_ERR_ARG; }
   if (((uintptr_t)d_text1 | (uintptr_t)d_text2) & (kChunk - 1)) { *err = "text pointers must be 16-byte aligned"; return KAIJU_GPU_ERR_ARG; }
   IngRec R{};
-  Carver measure{nullptr};
+  kjl::Carver measure{nullptr};
   carve(measure, R, d_text1, bytes1, d_text2, bytes2, rec_cap);
-  if (!*scratch) { *scratch = new (std::nothrow) kj_ingest_scratch(); if (!*scratch) { *err = "out of host memory"; return KAIJU_GPU_ERR_NOMEM; } }
-  kj_ingest_scratch *sc = *scratch;
-  if (measure.at + 256 > sc->cap) {
-    // (the passes of an earlier call on another stream may still use the old scratch)
-    if (sc->p) { if (hipDeviceSynchronize() != hipSuccess || hipFree(sc->p) != hipSuccess) { *err = "hipFree"; return KAIJU_GPU_ERR_HIP; } sc->p = nullptr; sc->cap = 0; }
-    const size_t want = measure.at + measure.at / 8 + 256;
-    if (hipMalloc(&sc->p, want) != hipSuccess) { (void)hipGetLastError(); *err = "hipMalloc of the ingest scratch"; return KAIJU_GPU_ERR_NOMEM; }
-    sc->cap = want;
-  }
-  Carver c{static_cast<uint8_t *>(sc->p)};
+  if (int rc = scratch.reserve(measure.at, 256, "hipMalloc of the ingest scratch", err)) return rc;
+  kjl::Carver c{static_cast<uint8_t *>(scratch.p)};
   carve(c, R, d_text1, bytes1, d_text2, bytes2, rec_cap);
   R.paired = paired ? 1 : 0; R.fastq = fastq ? 1 : 0; R.keep_names = keep_names ? 1 : 0; R.rec_cap = rec_cap;
   R.seqs = static_cast<uint8_t *>(d_seqs); R.off = d_off; R.names = d_names; R.info = d_info;
@@ -453,9 +389,7 @@ int kj_ingest_launch(kj_ingest_scratch **scratch, hipStream_t s, const void *d_t
   const dim3 tgrid((unsigned)std::min<uint64_t>(8192, (uint64_t)rec_cap / (kIngBlock / kTeam) + 1));
   const dim3 ogrid((unsigned)std::min<uint64_t>(2048, (2 * (uint64_t)rec_cap) / kScanBlock + 1));
   hipLaunchKernelGGL(k_ing_span_len, tgrid, blk, 0, s, R);
-  hipLaunchKernelGGL(k_ing_off_sums, ogrid, blk, 0, s, R);
-  hipLaunchKernelGGL(k_ing_off_top, dim3(1), blk, 0, s, R);
-  hipLaunchKernelGGL(k_ing_off_apply, ogrid, blk, 0, s, R);
+  kjl::launch_offsets(s, ogrid, IngMates{R}, R.mlen, R.oblk, R.oblk_base, R.off);
   hipLaunchKernelGGL(k_ing_span_copy, tgrid, blk, 0, s, R);
   hipLaunchKernelGGL(k_ing_finish, dim3(1), dim3(64), 0, s, R);
   if (hipGetLastError() != hipSuccess) { *err = "a kernel of the ingest passes could not be launched"; return KAIJU_GPU_ERR_HIP; }

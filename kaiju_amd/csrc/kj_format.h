@@ -254,15 +254,13 @@ inline bool build_pow_table(double *pw, uint32_t k) {
 
 // what format.hip offers capi.hip (the C-ABI of include/kaiju_gpu.h is defined there, next to the context)
 #if defined(__HIPCC__)
-struct kj_format_scratch;
-// queues every pass on `stream`; grows *scratch (created on the first call).  d_pw: the table of build_pow_table on the
-// device.  Returns 0, or a kaiju_gpu_status with *err set.
-int kj_format_launch(kj_format_scratch **scratch, hipStream_t stream, const kjf::Params &P, const double *d_pw,
+namespace kjl { struct Lines; }   // kj_lines.h: what a formatter keeps between calls
+// queues every pass on `stream`; grows st.mem, and leaves in st.written the device address of the number of bytes the passes
+// write (= text_bytes unless it overflows).  d_pw: the table of build_pow_table on the device.  Returns 0, or a
+// kaiju_gpu_status with *err set.
+int kj_format_launch(kjl::Lines &st, hipStream_t stream, const kjf::Params &P, const double *d_pw,
                      const kaiju_gpu_compact *d_recs, const uint64_t *d_off, uint32_t n, const void *d_text1, uint64_t bytes1,
                      const kaiju_gpu_name_span *d_names, void *d_out, uint64_t out_cap, kaiju_gpu_format_info *d_info, const char **err);
-// device address of the number of bytes the last launch wrote (= text_bytes unless it overflowed)
-const uint64_t *kj_format_written(const kj_format_scratch *scratch);
-void kj_format_free(kj_format_scratch *scratch);
 #endif
 
 #endif  // KJ_FORMAT_H

@@ -271,15 +271,11 @@ KJF_HD kaiju_gpu_format_names_info make_info(uint64_t total, uint32_t n, uint32_
 
 // what format_names.hip offers capi.hip
 #if defined(__HIPCC__)
-struct kj_fn_scratch;
-// queues every pass on `stream`; grows *scratch (created on the first call).  Returns 0, or a kaiju_gpu_status with *err set
-int kj_fn_launch(kj_fn_scratch **scratch, hipStream_t stream, const kjf::Params &P, const double *d_pw, const kaiju_gpu_compact *d_recs,
+// queues every pass on `stream`; grows st.mem, st.written as after kj_format_launch.  Returns 0, or a kaiju_gpu_status with *err set
+int kj_fn_launch(kjl::Lines &st, hipStream_t stream, const kjf::Params &P, const double *d_pw, const kaiju_gpu_compact *d_recs,
                  const uint64_t *d_off, uint32_t n, const void *d_text1, uint64_t bytes1, const kaiju_gpu_name_span *d_names,
                  const kaiju_gpu_taxon_names *names, int drop_unclassified, void *d_out, uint64_t out_cap, kaiju_gpu_format_names_info *d_info,
                  const char **err);
-// device address of the number of bytes the last launch wrote (= text_bytes unless it overflowed)
-const uint64_t *kj_fn_written(const kj_fn_scratch *scratch);
-void kj_fn_free(kj_fn_scratch *scratch);
 int kj_fn_device(const kaiju_gpu_taxon_names *names);
 #endif
 

@@ -282,17 +282,14 @@ KJF_HD uint32_t format_schunk(const Job &J, uint64_t c, uint32_t r_lo, uint32_t 
 
 // what format_seq.hip offers capi.hip
 #if defined(__HIPCC__)
-struct kj_fs_scratch;
-// in: the inputs of kjq::Job (everything up to nseq).  Queues init, lengths and offsets on `stream`; grows *scratch (created on
-// the first call).  Returns 0, or a kaiju_gpu_status with *err set.
-int kj_fs_lengths(kj_fs_scratch **scratch, hipStream_t stream, const kjq::Job &in, uint32_t n, const char **err);
-// device address of the size of the whole text the last kj_fs_lengths found
-const uint64_t *kj_fs_total(const kj_fs_scratch *scratch);
-// queues middle, write and finish behind the last kj_fs_lengths; the shadow (out_cap bytes) grows on demand
-int kj_fs_write(kj_fs_scratch *scratch, hipStream_t stream, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err);
-// device address of the number of bytes the last kj_fs_write wrote (= text_bytes unless it overflowed)
-const uint64_t *kj_fs_written(const kj_fs_scratch *scratch);
-void kj_fs_free(kj_fs_scratch *scratch);
+// J: the inputs of kjq::Job (everything up to nseq) set; the arrays of the passes are filled in here.  Queues init, lengths and
+// offsets on `stream`; grows st.mem, and leaves in st.total the device address of the size of the whole text.  Returns 0, or a
+// kaiju_gpu_status with *err set.
+int kj_fs_lengths(kjl::Lines &st, hipStream_t stream, kjq::Job &J, uint32_t n, const char **err);
+// queues middle, write and finish behind the kj_fs_lengths of the same J and n; the shadow (out_cap bytes) grows on demand.
+// st.written: the device address of the number of bytes written (= text_bytes unless it overflows)
+int kj_fs_write(kjl::Lines &st, hipStream_t stream, kjq::Job &J, uint32_t n, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info,
+                const char **err);
 #endif
 
 #endif  // KJ_FORMAT_SEQ_H

@@ -280,17 +280,14 @@ KJF_HD uint64_t written_bytes(const uint64_t *line_off, uint32_t n, uint64_t out
 
 // what format_verbose.hip offers capi.hip
 #if defined(__HIPCC__)
-struct kj_fv_scratch;
-// in: the inputs of kjv::Job (everything up to nseq).  Queues init, lengths and offsets on `stream`; grows *scratch (created on
-// the first call).  Returns 0, or a kaiju_gpu_status with *err set.
-int kj_fv_lengths(kj_fv_scratch **scratch, hipStream_t stream, const kjv::Job &in, uint32_t n, const char **err);
-// device address of the size of the whole text the last kj_fv_lengths found
-const uint64_t *kj_fv_total(const kj_fv_scratch *scratch);
-// queues middle, write and finish behind the last kj_fv_lengths; the shadow (out_cap bytes) grows on demand
-int kj_fv_write(kj_fv_scratch *scratch, hipStream_t stream, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info, const char **err);
-// device address of the number of bytes the last kj_fv_write wrote (= text_bytes unless it overflowed)
-const uint64_t *kj_fv_written(const kj_fv_scratch *scratch);
-void kj_fv_free(kj_fv_scratch *scratch);
+// J: the inputs of kjv::Job (everything up to nseq) set; the arrays of the passes are filled in here.  Queues init, lengths and
+// offsets on `stream`; grows st.mem, and leaves in st.total the device address of the size of the whole text.  Returns 0, or a
+// kaiju_gpu_status with *err set.
+int kj_fv_lengths(kjl::Lines &st, hipStream_t stream, kjv::Job &J, uint32_t n, const char **err);
+// queues middle, write and finish behind the kj_fv_lengths of the same J and n; the shadow (out_cap bytes) grows on demand.
+// st.written: the device address of the number of bytes written (= text_bytes unless it overflows)
+int kj_fv_write(kjl::Lines &st, hipStream_t stream, kjv::Job &J, uint32_t n, void *d_out, uint64_t out_cap, kaiju_gpu_format_verbose_info *d_info,
+                const char **err);
 #endif
 
 #endif  // KJ_FORMAT_VERBOSE_H

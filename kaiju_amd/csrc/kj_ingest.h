@@ -165,12 +165,11 @@ KJI_HD void put_letters(uint8_t *dst, const Chunk &v, uint32_t m) {
 #include <hip/hip_runtime.h>
 struct kaiju_gpu_name_span;
 struct kaiju_gpu_parse_info;
-struct kj_ingest_scratch;
-// queues every pass on `stream`; grows *scratch (created on the first call).  Returns 0, or a kaiju_gpu_status with *err set.
-int kj_ingest_launch(kj_ingest_scratch **scratch, hipStream_t stream, const void *d_text1, uint64_t bytes1, const void *d_text2,
+namespace kjl { struct Scratch; }   // kj_lines.h
+// queues every pass on `stream`; grows scratch.  Returns 0, or a kaiju_gpu_status with *err set.
+int kj_ingest_launch(kjl::Scratch &scratch, hipStream_t stream, const void *d_text1, uint64_t bytes1, const void *d_text2,
                      uint64_t bytes2, int fastq, int keep_names, uint32_t rec_cap, void *d_seqs, uint64_t *d_off,
                      kaiju_gpu_name_span *d_names, kaiju_gpu_parse_info *d_info, const char **err);
-void kj_ingest_free(kj_ingest_scratch *scratch);
 #endif
 
 #endif  // KJ_INGEST_H

@@ -1,7 +1,6 @@
-// kj_scan.h — the block scan the passes of ingest.hip and format.hip are built on (device only): an exclusive scan over the
-// 256 lanes of a block in lane order.  A prefix sum over more elements than one block is three kernels on top of it: the sum
-// of every block of kScanLanes elements, one block that walks those sums kScanLanes at a time, and a pass that adds the base
-// of its block to the scan inside the block (k_ing_off_sums / _top / _apply, k_fmt_off_sums / _top / _apply).
+// kj_scan.h — the block scan the passes of ingest.hip and of the formatters are built on (device only): an exclusive scan over
+// the 256 lanes of a block in lane order, for any associative operator (ingest.hip scans the transition functions of its FASTQ
+// state machine with it).  The prefix sum over more elements than one block - three kernels on top of it - is in kj_lines.h.
 #ifndef KJ_SCAN_H
 #define KJ_SCAN_H
 

@@ -7,27 +7,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <vector>
 
 #include "../../kaiju_amd/csrc/kj_format_names.h"
 #include "../../kaiju_amd/csrc/taxon_names.h"
+#include "lines_emu.h"
 
 using namespace kjn;
+using emu::Order;
 
 namespace {
-
-struct Order {
-  int mode; std::mt19937 rng;
-  std::vector<uint64_t> units(uint64_t n) {
-    std::vector<uint64_t> v(n);
-    std::iota(v.begin(), v.end(), 0);
-    if (mode == 1) std::reverse(v.begin(), v.end());
-    if (mode == 2) std::shuffle(v.begin(), v.end(), rng);
-    return v;
-  }
-};
 
 struct Built {
   Tab T{};
@@ -137,35 +126,15 @@ extern "C" int format_names_emu(const double *pw_in, const kaiju_gpu_compact *re
     n_inexact += (recs[r].info & KAIJU_HIT_INEXACT) ? 1 : 0;
     count[why]++;
   }
-  {                                                                           // k_fn_off_sums / _top / _apply
-    const uint64_t M = n, nb = (M + kScanBlock - 1) / kScanBlock;
-    std::vector<uint64_t> oblk(nb + 1, 0), obase(nb + 1, 0);
-    for (uint64_t b : o.units(nb)) { uint64_t t = 0; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) t += llen[i]; oblk[b] = t; }
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < nb; b++) { obase[b] = carry; carry += oblk[b]; }
-    line_off[M] = carry;
-    for (uint64_t b : o.units(nb)) { uint64_t t = obase[b]; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) { line_off[i] = t; t += llen[i]; } }
-  }
+  emu::scan_offsets(o, llen.data(), n, kScanBlock, line_off.data());          // kjl::k_scan_sums / _top / _apply
   const uint64_t total = line_off[n];
   // the output as the device sees it: 16-byte aligned, and not one byte longer than out_cap
   void *mem = nullptr;
   if (posix_memalign(&mem, kChunk, std::max<uint64_t>(out_cap, 1)) != 0) return -6;
   uint8_t *dev_out = static_cast<uint8_t *>(mem);
   if (out_cap) memcpy(dev_out, out, out_cap);
-  {                                                                           // k_fn_write
-    const uint64_t lim = std::min(total, out_cap), nb = (lim + kBlockBytes - 1) / kBlockBytes;
-    for (uint64_t b : o.units(nb)) {
-      uint32_t lo, hi;
-      block_records(line_off.data(), n, b, lim, &lo, &hi);
-      for (uint64_t l : o.units(kBlockLanes)) {
-        const uint64_t c = b * kBlockLanes + l;
-        if (c * kChunk >= lim) continue;
-        Chunk v;
-        const uint32_t m = format_chunk(c, text1, bytes1, names, line_off.data(), tax.data(), aslot.data(), T, lo, hi, total, out_cap, &v);
-        if (m) kjf::store_chunk(dev_out, c, v, m);
-      }
-    }
-  }
+  emu::write_blocks(o, line_off.data(), n, dev_out, out_cap,                  // k_fn_write
+                    [&](uint64_t c, uint32_t lo, uint32_t hi, uint64_t total, Chunk *v) { return format_chunk(c, text1, bytes1, names, line_off.data(), tax.data(), aslot.data(), T, lo, hi, total, out_cap, v); });
   if (out_cap) memcpy(out, dev_out, out_cap);
   free(mem);
   const kaiju_gpu_format_names_info fi = make_info(total, n, n_classified, n_inexact, out_cap, count[kWhyUnknown], count[kWhyUnnamed], count[kWhyDropped]);   // k_fn_finish

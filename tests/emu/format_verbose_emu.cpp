@@ -11,26 +11,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <vector>
 
 #include "../../kaiju_amd/csrc/kj_format_verbose.h"
+#include "lines_emu.h"
 
 using namespace kjv;
+using emu::Order;
 
 namespace {
-
-struct Order {
-  int mode; std::mt19937 rng;
-  std::vector<uint64_t> units(uint64_t n) {
-    std::vector<uint64_t> v(n);
-    std::iota(v.begin(), v.end(), 0);
-    if (mode == 1) std::reverse(v.begin(), v.end());
-    if (mode == 2) std::shuffle(v.begin(), v.end(), rng);
-    return v;
-  }
-};
 
 // lane k of the team as the rows hold it (the lane's own copy is not looked at)
 struct TeamRows {
@@ -94,15 +83,7 @@ extern "C" int format_verbose_emu(const uint64_t *a, const double *d, int order,
     hdr.n_inexact += (J.recs[r].info & KAIJU_HIT_INEXACT) ? 1 : 0;
     hdr.n_truncated += h.truncated;
   }
-  {                                                                           // k_fv_off_sums / _top / _apply
-    const uint64_t M = n, nb = (M + kScanBlock - 1) / kScanBlock;
-    std::vector<uint64_t> oblk(nb + 1, 0), obase(nb + 1, 0);
-    for (uint64_t b : o.units(nb)) { uint64_t t = 0; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) t += llen[i]; oblk[b] = t; }
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < nb; b++) { obase[b] = carry; carry += oblk[b]; }
-    line_off[M] = carry;
-    for (uint64_t b : o.units(nb)) { uint64_t t = obase[b]; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) { line_off[i] = t; t += llen[i]; } }
-  }
+  emu::scan_offsets(o, llen.data(), n, kScanBlock, line_off.data());          // kjl::k_scan_sums / _top / _apply
   const uint64_t total = line_off[n];
   // the output and its shadow as the device sees them: 16-byte aligned, and not one byte longer than out_cap
   void *mem = nullptr;
@@ -121,20 +102,8 @@ extern "C" int format_verbose_emu(const uint64_t *a, const double *d, int order,
     for (uint64_t i : o.units(kTeam))
       mid_lane(J, h, T.lane[i], (uint32_t)i, T.id_off[i], T.ids_len[i], T.klen[i], T.acc_off[i], T.accs_len[i], shadow + line_off[r] + 3 + h.name.len);
   }
-  {                                                                           // k_fv_write
-    const uint64_t lim = std::min(total, J.out_cap), nb = (lim + kBlockBytes - 1) / kBlockBytes;
-    for (uint64_t b : o.units(nb)) {
-      uint32_t lo, hi;
-      kjf::block_records(line_off.data(), n, b, lim, &lo, &hi);
-      for (uint64_t l : o.units(kBlockLanes)) {
-        const uint64_t c = b * kBlockLanes + l;
-        if (c * kChunk >= lim) continue;
-        Chunk v;
-        const uint32_t m = format_vchunk(J, c, lo, hi, total, &v);
-        if (m) kjf::store_chunk(J.out, c, v, m);
-      }
-    }
-  }
+  emu::write_blocks(o, line_off.data(), n, J.out, J.out_cap,                  // k_fv_write
+                    [&](uint64_t c, uint32_t lo, uint32_t hi, uint64_t total, Chunk *v) { return format_vchunk(J, c, lo, hi, total, v); });
   if (J.out_cap) memcpy(out, J.out, J.out_cap);
   hdr.written = written_bytes(line_off.data(), n, J.out_cap);                 // k_fv_finish
   const kaiju_gpu_format_verbose_info fi = make_info(total, hdr, J.out_cap);

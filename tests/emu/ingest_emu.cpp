@@ -4,13 +4,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <vector>
 
 #include "../../kaiju_amd/csrc/kj_ingest.h"
+#include "lines_emu.h"
 
 using namespace kji;
+using emu::Order;
 
 namespace {
 
@@ -26,17 +26,6 @@ struct File {
   Hdr hdr;
 };
 
-struct Order {
-  int mode; std::mt19937 rng;
-  std::vector<uint64_t> tiles(uint64_t n) {
-    std::vector<uint64_t> v(n);
-    std::iota(v.begin(), v.end(), 0);
-    if (mode == 1) std::reverse(v.begin(), v.end());
-    if (mode == 2) std::shuffle(v.begin(), v.end(), rng);
-    return v;
-  }
-};
-
 // out[i] = in[0] + .. + in[i - 1], i <= n (k_ing_top_u32)
 void top_u32(const std::vector<uint32_t> &in, std::vector<uint32_t> &out, uint32_t n, uint32_t *total) {
   uint32_t carry = 0;
@@ -46,13 +35,13 @@ void top_u32(const std::vector<uint32_t> &in, std::vector<uint32_t> &out, uint32
 }
 
 void lines(File &f, Order &o) {
-  for (uint64_t t : o.tiles(f.n_tiles)) {                                     // k_ing_lines_count
+  for (uint64_t t : o.units(f.n_tiles)) {                                     // k_ing_lines_count
     uint32_t tot = 0;
     for (uint32_t l = 0; l < kTileLanes; l++) tot += popc16(nl_mask(f.text, f.bytes, t * kTileLanes + l));
     f.tile_cnt[t] = tot;
   }
   top_u32(f.tile_cnt, f.tile_base, f.n_tiles, nullptr);
-  for (uint64_t t : o.tiles(std::max(1u, f.n_tiles))) {                       // k_ing_lines_fill
+  for (uint64_t t : o.units(std::max(1u, f.n_tiles))) {                       // k_ing_lines_fill
     uint32_t ex = 0;
     for (uint32_t l = 0; l < kTileLanes && t < f.n_tiles; l++) {
       const uint64_t c = t * kTileLanes + l;
@@ -89,7 +78,7 @@ void records(File &f, Order &o, int fastq, uint32_t rec_cap) {
     return;
   }
   if (fastq) {
-    for (uint64_t b : o.tiles(nb)) {                                          // k_ing_fq_func
+    for (uint64_t b : o.units(nb)) {                                          // k_ing_fq_func
       uint32_t tot = kFqIdent;
       for (uint32_t l = 0; l < kScanBlock; l++) {
         const uint32_t i = (uint32_t)b * kScanBlock + l;
@@ -99,7 +88,7 @@ void records(File &f, Order &o, int fastq, uint32_t rec_cap) {
     }
     uint32_t carry = kFqIdent;                                                // k_ing_fq_top
     for (uint32_t b = 0; b < nb; b++) { f.blk_base[b] = fq_apply(carry, 0); carry = fq_compose(carry, f.blk[b]); }
-    for (uint64_t b : o.tiles(nb)) {                                          // k_ing_fq_flag
+    for (uint64_t b : o.units(nb)) {                                          // k_ing_fq_flag
       uint32_t ex = kFqIdent, cnt = 0;
       for (uint32_t l = 0; l < kScanBlock; l++) {
         const uint32_t i = (uint32_t)b * kScanBlock + l;
@@ -112,7 +101,7 @@ void records(File &f, Order &o, int fastq, uint32_t rec_cap) {
       f.blk[b] = cnt;
     }
   } else {
-    for (uint64_t b : o.tiles(nb)) {                                          // k_ing_fa_flag
+    for (uint64_t b : o.units(nb)) {                                          // k_ing_fa_flag
       uint32_t cnt = 0;
       for (uint32_t l = 0; l < kScanBlock; l++) {
         const uint32_t i = (uint32_t)b * kScanBlock + l;
@@ -124,7 +113,7 @@ void records(File &f, Order &o, int fastq, uint32_t rec_cap) {
     }
   }
   top_u32(f.blk, f.blk_base, nb, &f.hdr.n_records);
-  for (uint64_t b : o.tiles(nb)) {                                            // k_ing_rec_scatter
+  for (uint64_t b : o.units(nb)) {                                            // k_ing_rec_scatter
     uint32_t r = f.blk_base[b];
     for (uint32_t l = 0; l < kScanBlock; l++) {
       const uint32_t i = (uint32_t)b * kScanBlock + l;
@@ -180,7 +169,7 @@ extern "C" int ingest_emu(const uint8_t *t1, uint64_t b1, const uint8_t *t2, uin
   const uint32_t n1 = f1.hdr.n_records, n2 = paired ? f2.hdr.n_records : n1, n = std::min(std::min(n1, n2), rec_cap);
   std::vector<uint32_t> mlen(2 * (size_t)n + 1, 0);
   uint32_t max_mate = 0, mismatch = kNone;
-  for (uint64_t r64 : o.tiles(n)) {                                           // k_ing_span_len
+  for (uint64_t r64 : o.units(n)) {                                           // k_ing_span_len
     const uint32_t r = (uint32_t)r64;
     const uint32_t c1 = count_letters(f1.text, seq_span(f1.line_start.data(), f1.rec_line.data(), r, n1, f1.hdr.n_lines, f1.bytes, fastq != 0));
     uint32_t p1, l1, c2 = 0;
@@ -195,16 +184,8 @@ extern "C" int ingest_emu(const uint8_t *t1, uint64_t b1, const uint8_t *t2, uin
     names[2 * (size_t)r] = p1; names[2 * (size_t)r + 1] = l1;
     max_mate = std::max(max_mate, std::max(c1, c2));
   }
-  {                                                                           // k_ing_off_sums / _top / _apply
-    const uint64_t M = 2 * (uint64_t)n, nb = (M + kScanBlock - 1) / kScanBlock;
-    std::vector<uint64_t> oblk(nb + 1, 0), obase(nb + 1, 0);
-    for (uint64_t b : o.tiles(nb)) { uint64_t t = 0; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) t += mlen[i]; oblk[b] = t; }
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < nb; b++) { obase[b] = carry; carry += oblk[b]; }
-    off[M] = carry;
-    for (uint64_t b : o.tiles(nb)) { uint64_t t = obase[b]; for (uint64_t i = b * kScanBlock; i < std::min(M, (b + 1) * kScanBlock); i++) { off[i] = t; t += mlen[i]; } }
-  }
-  for (uint64_t r64 : o.tiles(n)) {                                           // k_ing_span_copy
+  emu::scan_offsets(o, mlen.data(), 2 * (uint64_t)n, kScanBlock, off);        // kjl::k_scan_sums / _top / _apply
+  for (uint64_t r64 : o.units(n)) {                                           // k_ing_span_copy
     const uint32_t r = (uint32_t)r64;
     copy_letters(f1.text, seq_span(f1.line_start.data(), f1.rec_line.data(), r, n1, f1.hdr.n_lines, f1.bytes, fastq != 0), seqs + off[2 * (size_t)r]);
     if (paired)

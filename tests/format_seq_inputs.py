@@ -30,6 +30,7 @@ I_EMPTY, I_ONE, I_15, I_16, I_17, I_33, I_ODD, I_Q0 = range(8)
 NO_SEQ = 1000000                      # a sequence number no index of these names has
 INEXACT = 0x80000000
 RECORD_COUNTS = (0, 1, 2, 3, 63, 64, 65, 255, 256, 257)
+BIG_COUNT = 256 * 256 + 1             # more records than one step of the block on top of the prefix sum takes
 BEST_VALUES = (0, 9, 10, 99999, 4294967295)
 M, MIN_SCORE = 11, 65                 # the defaults of -m and -s
 PEP_ALPHABET = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY,", dtype=np.uint8)
@@ -108,6 +109,11 @@ def _counts(n, seed):
         else:
             out.append(U(b"r%d" % i, lens=(150 if x < 0.75 else 20, 0)))
     return out
+
+
+def _big(n):
+    """short names, one matched sequence per record, a 'U' record now and then: n records cost little"""
+    return [U(b"r%d" % i) if i % 7 == 3 else rec(b"r%d" % i, best=11 + i % 89, ids=(i % len(DB_NAMES),)) for i in range(n)]
 
 
 def _ids():
@@ -195,6 +201,8 @@ def cases(B, S, K, index_db):
     c = []
     for n in RECORD_COUNTS:
         c.append(make("n_%d" % n, _counts(n, 200 + n)))
+    assert BIG_COUNT == S * S + 1
+    c.append(make("n_%d" % BIG_COUNT, _big(BIG_COUNT), with_pep=False))
     c.append(make("ids", _ids()))
     c.append(make("ids_plain", _ids(), with_pep=False))                 # without -v: every 'C' line ends ",\t\n"
     c.append(make("texts", _texts(40), text_cap=40))

@@ -16,6 +16,7 @@ GOLDEN_NAMES = os.path.join(NAMES_DIR, "golden", "names.dmp")
 RANKS_DEEP, RANKS_GOLDEN = "ranks:genus,species,phylum,genus", "ranks:family,genus,species"
 MODES = ("name", "path", RANKS_DEEP)
 VARIANTS = [(m, d) for m in MODES for d in (False, True)]          # mode, drop_unclassified
+BIG_COUNT = 256 * 256 + 1             # more records than one step of the block on top of the prefix sum takes
 
 
 def read(path):
@@ -45,6 +46,13 @@ def drawn(n, seed=7):
     recs = [(0, 5, 1) if rng.random() < 0.2 else (t, 5, 1) for t in pick]
     names = [b"d%d" % i + b"n" * int(rng.integers(0, 38)) for i in range(n)]
     return format_inputs.make("drawn_%d" % n, names, recs)
+
+
+def big():
+    """BIG_COUNT records with short names and a one-digit taxon each (0: not classified; 1, 7 and 9 are nodes of deep/, the others
+    are unknown there)"""
+    n = BIG_COUNT
+    return format_inputs.make("big_%d" % n, [b"b%d" % i for i in range(n)], [(i % 10, 5, 1) for i in range(n)])
 
 
 def capacity_jobs(cases, expect):

@@ -123,6 +123,17 @@ def test_every_input_in_every_variant_and_order(emu, trees, inputs, base, golden
     assert all(v > 0 for v in seen.values()), seen
 
 
+def test_second_step_of_the_scan_at_the_exact_capacity(emu, trees, golden):
+    """more records than the one block on top of the prefix sum takes in a step, into a buffer of exactly the text's length"""
+    case = names_inputs.big()
+    assert len(case["recs"]) > constants(emu)[1] ** 2
+    handle, expect = trees["path"]
+    want = names_expect.expected(expect, format_expect.expected(case, db_of(case, golden)), False)
+    assert want["info"]["n_unknown_taxon"] > 0 and b"\tLineage 9; \n" in want["text"]
+    out, info = run_emu(emu, case, handle, False, db_of(case, golden), len(want["text"]), 2, seed=8)
+    compare(out, info, want, case["id"])
+
+
 def test_capacity(emu, trees, inputs, base, golden):
     jobs = names_inputs.capacity_jobs(inputs, lambda k, m, d: names_expect.expected(trees[m][1], base[k["id"]], d))
     assert len(jobs) == 4 * (2 * 6 + 2 * 5)

@@ -100,11 +100,14 @@ def compare(out, info, want, what):
     assert np.all(out[w:] == 0xA5), (what, "bytes behind the lines written")
 
 
-def test_the_inputs_hold_what_they_claim(inputs, want_of):
+def test_the_inputs_hold_what_they_claim(emu, inputs, want_of):
     """from the rules alone: every kind of line, both outcomes of the gate, the fragments of the kaijup rule, truncated and inexact
     records, every alignment of the copied segments"""
     by_id = {k["id"]: k for k in inputs}
-    assert [len(by_id["n_%d" % n]["hits"]) for n in fsi.RECORD_COUNTS] == list(fsi.RECORD_COUNTS)
+    counts = fsi.RECORD_COUNTS + (fsi.BIG_COUNT,)
+    assert [len(by_id["n_%d" % n]["hits"]) for n in counts] == list(counts) and fsi.BIG_COUNT > constants(emu)[1] ** 2
+    big = want_of(by_id["n_%d" % fsi.BIG_COUNT])["info"]
+    assert 0 < big["n_records"] - big["n_classified"] < big["n_classified"]
     assert sorted(len(nm) for nm in fsi.DB_NAMES[:6]) == list(fsi.TABLE_NAME_LENGTHS) and all(c in fsi.DB_NAMES[fsi.I_ODD] for c in b"_,\t")
     for n in (65, 257):
         t = want_of(by_id["n_%d" % n])["text"]
@@ -166,6 +169,14 @@ def test_every_input_in_every_order(emu, inputs, want_of):
         for order in (0, 1, 2):
             out, info = run_emu(emu, case, len(want["text"]) + 5, order, seed=3 + order)
             compare(out, info, want, (case["id"], order))
+
+
+def test_second_step_of_the_scan_at_the_exact_capacity(emu, inputs, want_of):
+    """more records than the one block on top of the prefix sum takes in a step, into a buffer of exactly the text's length"""
+    case = [k for k in inputs if k["id"] == "n_%d" % fsi.BIG_COUNT][0]
+    want = want_of(case)
+    out, info = run_emu(emu, case, len(want["text"]), 2, seed=8)
+    compare(out, info, want, case["id"])
 
 
 def test_capacity(emu, inputs, want_of):

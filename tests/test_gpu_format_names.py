@@ -112,6 +112,17 @@ def test_format_names_on_every_input(ctx, trees, inputs, base):
     assert len(want["text"]) > 100 * 4096 and b"L" * 300 in want["text"] and np.diff(want["line_off"]).max() > 1000
 
 
+def test_second_step_of_the_scan_at_the_exact_capacity(ctx, trees):
+    """more records than the one block on top of the prefix sum takes in a step, into a buffer of exactly the text's length"""
+    case = names_inputs.big()
+    dev, expect, _ = trees["path"]
+    want = names_expect.expected(expect, format_expect.expected(case, ctx.index.db_length), False)
+    cap = len(want["text"])
+    out = np.full(cap + 32, 0xA5, dtype=np.uint8)
+    out, info = ctx.for_case(case).format_names(case["recs"], case["off"], case["text1"], case["names"], dev, out_cap=cap, out=out)
+    compare(out, info, want, case["id"])
+
+
 def test_format_names_capacity(ctx, trees, inputs, base):
     jobs = names_inputs.capacity_jobs(inputs, lambda k, m, d: names_expect.expected(trees[m][1], base[k["id"]], d))
     assert len(jobs) == 4 * (2 * 6 + 2 * 5)

@@ -135,8 +135,8 @@ def test_device_pointer_form(small, inputs, want_of):
     stream = hip.stream()
     ids = ("n_3", "u_protein_greedy", "ids_plain", "n_257", "alignment_grid", "n_3")
     jobs = [(k, cap) for k, cap in fsi.capacity_cases(inputs, want_of) if k["id"] in ids]
-    jobs += [(k, None) for i in ids for k in inputs if k["id"] == i] + [(k, None) for k in inputs if k["id"] in ("n_0", "gate_pairs_nt_db_golden_E_0.01")]
-    assert len(jobs) == 5 * 8 + 6 + 2
+    jobs += [(k, None) for i in ids for k in inputs if k["id"] == i] + [(k, None) for k in inputs if k["id"] in ("n_0", "n_%d" % fsi.BIG_COUNT, "gate_pairs_nt_db_golden_E_0.01")]
+    assert len(jobs) == 5 * 8 + 6 + 3
     contexts = set()
     for case, cap in jobs:
         want = fse.expected(case, small.index.db_length, cap, db_names=small.db_names)
