@@ -549,6 +549,47 @@ int kaiju_gpu_classify_text_to_text_names(kaiju_gpu_ctx *ctx, const kaiju_gpu_ta
                                           const kaiju_gpu_taxon_names *names, int drop_unclassified, char *out_text, uint64_t out_cap,
                                           kaiju_gpu_parse_info *info_parse, kaiju_gpu_format_names_info *info_format);
 
+/* ---- kaiju-addTaxonNames on existing output text: lines in, annotated lines out ------------------------------- */
+/* The column above for lines that exist already - an earlier run's, those of kaiju -v, kaijux / kaijup, the reference's own
+   kaiju (kaiju_amd/csrc/annotate.hip; the rules: kj_annotate.h, those of kaiju-addTaxonNames.cpp:133-228):
+     - a line ends at '\n'; the last one may lack it and gets one; a line of length 0 gives nothing; every other byte, '\r' and
+       NUL included, is a byte of the line
+     - byte 0 is not 'C': the line is copied unchanged, or left out with drop_unclassified (the tool's -u)
+     - a 'C' line: the id is the run of [0-9] directly behind the second tab, whatever follows it ("7abc", "7\t..." read 7).
+       Fewer than two tabs, an empty run, a value above 2^64 - 1 (by value), an id that is no node, a node without a name of
+       its own: the line is copied unchanged, also under drop_unclassified
+     - else: line "\t" annotation "\n", the annotation that of kaiju_gpu_format_names in the mode of `names`
+   The annotator is scratch on the device of `names`; it needs no index and no context.  One call at a time per annotator. */
+typedef struct kaiju_gpu_annotator kaiju_gpu_annotator;
+int kaiju_gpu_annotator_create(const kaiju_gpu_taxon_names *names, kaiju_gpu_annotator **out);
+void kaiju_gpu_annotator_free(kaiju_gpu_annotator *a);
+typedef struct kaiju_gpu_annotate_info {
+  uint64_t text_bytes;             /* size of the whole annotated text, also when it overflowed                            */
+  uint32_t n_lines;                /* lines of the input, those of length 0 included                                       */
+  uint32_t n_c_lines;              /* lines whose byte 0 is 'C'                                                            */
+  uint32_t n_annotated;            /* ... that got the column                                                              */
+  uint32_t n_bad_id;               /* ... without a readable id: fewer than two tabs, no digit, above 2^64 - 1             */
+  uint32_t n_unknown_taxon;        /* ... whose id is no node of the tree                                                  */
+  uint32_t n_unnamed_taxon;        /* ... whose node has no name                                                           */
+  uint32_t n_dropped;              /* other lines left out (drop_unclassified)                                             */
+  uint32_t n_empty;                /* lines of length 0                                                                    */
+  uint32_t overflow;
+  uint32_t reserved;
+} kaiju_gpu_annotate_info;         /* 48 bytes */
+/* All pointers device pointers; every pass is queued on `stream` and nothing synchronises, so d_text may be the d_out of
+   kaiju_gpu_format_verbose_device / _seq_device / _compact_device queued on the same stream in front of it.  d_text and d_out
+   are 16-byte aligned and d_text is readable up to the next multiple of 16 behind bytes (KAIJU_GPU_ERR_ARG otherwise, as for
+   bytes above 2^32 - 16).  bytes == 0 writes nothing.  Lines are written whole or not at all, no byte at or behind out_cap is
+   touched.  The scratch - 24 bytes per byte of text, sized for a text of nothing but '\n' - lives in the annotator. */
+int kaiju_gpu_annotate_text_device(kaiju_gpu_annotator *a, const void *d_text, uint64_t bytes, int drop_unclassified,
+                                   void *d_out, uint64_t out_cap, kaiju_gpu_annotate_info *d_info, void *stream);
+/* The same for host memory (no alignment asked for): upload, the passes, the download of the lines written */
+int kaiju_gpu_annotate_text(kaiju_gpu_annotator *a, const char *text, uint64_t bytes, int drop_unclassified,
+                            char *out, uint64_t out_cap, kaiju_gpu_annotate_info *info);
+/* Host only: an out_cap that cannot overflow for a text of n_lines lines (its '\n' bytes plus one):
+   bytes + 1 + n_lines * (1 + max_annotation) */
+uint64_t kaiju_gpu_annotate_bound(uint64_t bytes, uint64_t n_lines, const kaiju_gpu_taxon_names *names);
+
 /* ---- the lines of kaiju -v on the device: hits and matches in, text out ------------------------------------ */
 /* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi WITH -v, as HIP passes
    (kaiju_amd/csrc/format_verbose.hip; the rules: kj_format_verbose.h): the decision of the three-column lines, and for a

@@ -80,6 +80,10 @@ FORMAT_NAMES_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"),
                                     ("n_unknown_taxon", "<u4"), ("n_unnamed_taxon", "<u4"), ("n_dropped", "<u4"), ("reserved", "<u4")])
 assert FORMAT_NAMES_INFO_DTYPE.itemsize == 40
 NAMES_NAME, NAMES_PATH, NAMES_RANKS = 0, 1, 2
+ANNOTATE_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_lines", "<u4"), ("n_c_lines", "<u4"), ("n_annotated", "<u4"), ("n_bad_id", "<u4"),
+                                ("n_unknown_taxon", "<u4"), ("n_unnamed_taxon", "<u4"), ("n_dropped", "<u4"), ("n_empty", "<u4"), ("overflow", "<u4"),
+                                ("reserved", "<u4")])
+assert ANNOTATE_INFO_DTYPE.itemsize == 48
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -200,6 +204,13 @@ def lib():
         L.kaiju_gpu_format_names_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_void_p]
         L.kaiju_gpu_classify_text_to_text_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
                                                             C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    if hasattr(L, "kaiju_gpu_annotator_create"):              # (likewise)
+        L.kaiju_gpu_annotator_create.argtypes = [C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_annotator_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_annotate_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_annotate_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_annotate_bound.restype = C.c_uint64
+        L.kaiju_gpu_annotate_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -468,6 +479,58 @@ class DeviceTaxonNames:
     def close(self):
         if self._h:
             lib().kaiju_gpu_taxon_names_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Annotator:
+    """kaiju-addTaxonNames on the device of ``dnames`` (kaiju_gpu_annotator_create): text of output lines in, annotated text
+    out.  It needs no index and no Classifier."""
+
+    def __init__(self, dnames: DeviceTaxonNames):
+        if not hasattr(lib(), "kaiju_gpu_annotator_create"):
+            raise KaijuGpuError("this library was linked without annotate.hip")
+        self._names = dnames                                  # (the tables must outlive the annotator)
+        self._h = C.c_void_p()
+        _check(lib().kaiju_gpu_annotator_create(dnames._h, C.byref(self._h)))
+
+    def bound(self, text) -> int:
+        return int(lib().kaiju_gpu_annotate_bound(len(text), bytes(text).count(b"\n") + 1, self._names._h))
+
+    def annotate(self, text, drop_unclassified=False, out_cap=None, out=None):
+        """Returns (bytes, info): the annotated lines and an ANNOTATE_INFO_DTYPE record.  out_cap: the capacity (default: one
+        that cannot overflow); when the text overflows it, info["overflow"] is set and only whole lines in front of it are
+        written.  out: a uint8 array of at least out_cap bytes to write into - the lines written change, nothing else does -;
+        the first value returned is then None"""
+        text = bytes(text)
+        cap = int(out_cap) if out_cap is not None else self.bound(text)
+        own = out is None
+        if own:
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.size >= cap
+        info = np.zeros(1, dtype=ANNOTATE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_annotate_text(self._h, text, len(text), 1 if drop_unclassified else 0, out.ctypes.data, cap, info.ctypes.data))
+        if not own:
+            return None, info[0]
+        written = min(int(info[0]["text_bytes"]), cap)
+        if info[0]["overflow"]:                               # (the buffer was zeroed: behind the last line written lies no newline)
+            written = bytes(out[:written]).rfind(b"\n") + 1
+        return bytes(out[:written]), info[0]
+
+    def annotate_device(self, d_text_ptr: int, nbytes: int, d_out_ptr: int, out_cap: int, d_info_ptr: int, drop_unclassified=False, stream: int = 0):
+        """the same for device-resident buffers (raw pointers, both 16-byte aligned): kaiju_gpu_annotate_text_device,
+        asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_annotate_text_device(self._h, d_text_ptr or None, nbytes, 1 if drop_unclassified else 0, d_out_ptr or None, out_cap,
+                                                    d_info_ptr or None, stream or None))
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_annotator_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

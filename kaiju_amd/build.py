@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkaiju_gpu.so")
-SOURCES = ["capi.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
-HEADERS = ["kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
+SOURCES = ["capi.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "annotate.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
+HEADERS = ["kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "kj_annotate.h", "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-gpu-rdc", "-Wno-unused-result"]
 
@@ -71,6 +71,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
     build_cli(force=force, verbose=verbose)
+    build_annotate_cli(force=force, verbose=verbose)
     return LIB
 
 
@@ -97,6 +98,22 @@ def build_cli(force=False, verbose=False):
     _sh.copy2(CLI, os.path.join(os.path.dirname(CLI), "kaijux"))      # kaijux: database sequences instead of taxa
     _sh.copy2(CLI, os.path.join(os.path.dirname(CLI), "kaijup"))      # kaijup: kaijux for protein reads
     return CLI
+
+
+ANNOTATE_SRC = [os.path.join(CSRC, "host", f) for f in ("annotate_main.cpp", "annotate_blocks.h")]
+ANNOTATE_CLI = os.path.join(HERE, "bin", "kaiju-addTaxonNames")
+
+
+def build_annotate_cli(force=False, verbose=False):
+    """the drop-in `kaiju-addTaxonNames` command (host C++ over the C-ABI)"""
+    if not force and os.path.exists(ANNOTATE_CLI) and os.path.getmtime(ANNOTATE_CLI) >= max([os.path.getmtime(LIB)] + [os.path.getmtime(s) for s in ANNOTATE_SRC]):
+        return ANNOTATE_CLI
+    os.makedirs(os.path.dirname(ANNOTATE_CLI), exist_ok=True)
+    cmd = ["g++", "-O2", "-std=c++17", "-o", ANNOTATE_CLI, ANNOTATE_SRC[0], "-L" + HERE, "-lkaiju_gpu", "-lpthread", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return ANNOTATE_CLI
 
 
 if __name__ == "__main__":

@@ -211,6 +211,7 @@ extern "C" int kaiju_gpu_taxon_names_upload(const kaiju_taxon_names *names, int 
 extern "C" void kaiju_gpu_taxon_names_free(kaiju_gpu_taxon_names *names) { delete names; }
 extern "C" uint64_t kaiju_gpu_taxon_names_max_annotation(const kaiju_gpu_taxon_names *names) { return names ? names->max_annotation : 0; }
 int kj_fn_device(const kaiju_gpu_taxon_names *names) { return names ? names->device : -1; }
+const kjn::Tab *kj_fn_tab(const kaiju_gpu_taxon_names *names) { return names ? &names->tab : nullptr; }   // (for annotate.hip)
 
 extern "C" int kaiju_gpu_taxon_names_read(const kaiju_gpu_taxon_names *names, int which, void *host_out, uint64_t out_bytes, uint64_t *n_slots) {
   if (!names || (!host_out && out_bytes)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
