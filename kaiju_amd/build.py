@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkaiju_gpu.so")
-SOURCES = ["capi.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "annotate.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
-HEADERS = ["kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "kj_annotate.h", "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
+SOURCES = ["capi.hip", "capi_index.hip", "capi_text.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "annotate.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
+HEADERS = ["capi_internal.h", "kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "kj_annotate.h", "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-gpu-rdc", "-Wno-unused-result"]
 

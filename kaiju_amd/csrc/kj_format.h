@@ -252,7 +252,7 @@ inline bool build_pow_table(double *pw, uint32_t k) {
 }
 }  // namespace kjf
 
-// what format.hip offers capi.hip (the C-ABI of include/kaiju_gpu.h is defined there, next to the context)
+// what format.hip offers capi_text.hip (the entry points of include/kaiju_gpu.h are defined there)
 #if defined(__HIPCC__)
 namespace kjl { struct Lines; }   // kj_lines.h: what a formatter keeps between calls
 // queues every pass on `stream`; grows st.mem, and leaves in st.written the device address of the number of bytes the passes

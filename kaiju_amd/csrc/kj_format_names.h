@@ -269,7 +269,7 @@ KJF_HD kaiju_gpu_format_names_info make_info(uint64_t total, uint32_t n, uint32_
 
 }  // namespace kjn
 
-// what format_names.hip offers capi.hip
+// what format_names.hip offers capi_text.hip
 #if defined(__HIPCC__)
 // queues every pass on `stream`; grows st.mem, st.written as after kj_format_launch.  Returns 0, or a kaiju_gpu_status with *err set
 int kj_fn_launch(kjl::Lines &st, hipStream_t stream, const kjf::Params &P, const double *d_pw, const kaiju_gpu_compact *d_recs,

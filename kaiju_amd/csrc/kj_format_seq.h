@@ -280,7 +280,7 @@ KJF_HD uint32_t format_schunk(const Job &J, uint64_t c, uint32_t r_lo, uint32_t 
 
 }  // namespace kjq
 
-// what format_seq.hip offers capi.hip
+// what format_seq.hip offers capi_text.hip
 #if defined(__HIPCC__)
 // J: the inputs of kjq::Job (everything up to nseq) set; the arrays of the passes are filled in here.  Queues init, lengths and
 // offsets on `stream`; grows st.mem, and leaves in st.total the device address of the size of the whole text.  Returns 0, or a

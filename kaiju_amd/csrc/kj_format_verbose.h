@@ -278,7 +278,7 @@ KJF_HD uint64_t written_bytes(const uint64_t *line_off, uint32_t n, uint64_t out
 
 }  // namespace kjv
 
-// what format_verbose.hip offers capi.hip
+// what format_verbose.hip offers capi_text.hip
 #if defined(__HIPCC__)
 // J: the inputs of kjv::Job (everything up to nseq) set; the arrays of the passes are filled in here.  Queues init, lengths and
 // offsets on `stream`; grows st.mem, and leaves in st.total the device address of the size of the whole text.  Returns 0, or a

@@ -160,7 +160,7 @@ KJI_HD void put_letters(uint8_t *dst, const Chunk &v, uint32_t m) {
 
 }  // namespace kji
 
-// what ingest.hip offers capi.hip (the C-ABI of include/kaiju_gpu.h is defined there, next to the context)
+// what ingest.hip offers capi_text.hip (the entry points of include/kaiju_gpu.h are defined there)
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 struct kaiju_gpu_name_span;

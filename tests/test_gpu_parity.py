@@ -616,7 +616,7 @@ def test_greedy_row_pool_lane(gpu_lib, golden, big, split, tmp_path):
     import sys
     api = gpu_lib
     lib = os.path.join(util.ROOT, "kaiju_amd", "variants", "libkaiju_gpu_g3.so")
-    deps = [os.path.join(util.ROOT, "kaiju_amd", "csrc", f) for f in ("capi.hip", "kj_core.h", "kj_greedy3.h")]
+    deps = [os.path.join(util.ROOT, "kaiju_amd", "csrc", f) for f in ("capi.hip", "capi_index.hip", "capi_text.hip", "capi_internal.h", "kj_core.h", "kj_greedy3.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.run(["bash", os.path.join(util.ROOT, "tests", "tools", "mem_variants.sh"), "build"], check=True,
                        env=dict(os.environ, VARIANTS="g3"))
@@ -708,3 +708,31 @@ def test_verbose_packed_equals_strided(gpu_lib, golden, gidx, mode):
     h0, v0, p0, s0 = clf.classify_verbose_packed(np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64))
     assert len(h0) == 0 and s0 == b""
     clf.close()
+
+
+@pytest.mark.parametrize("wide", ["", "17"])
+def test_mem_lane_instantiations_agree(gpu_lib, golden, wide, monkeypatch):
+    """the second-generation MEM kernels share one set-up of their lane (capi.hip: mem2_scratch<WIDE, VERBOSE>): on the golden
+    reads, single and paired, the counting instantiation (k_mem_count / k_mem_wide2_count) and the one of kaiju -v (k_mem_vb /
+    k_mem_wide2_vb) write the best, n_ids, flags and taxid of the plain one (k_mem / k_mem_wide2), narrow and with
+    KAIJU_GPU_FORCE_WIDE=17.  The pair in the list order of kaijux (k_mem_x / k_mem_wide2_x) is compared with the oracle by
+    test_gpu_zz_protein_kaijux_mem.py: test_kaijux_mem_order_under_the_id_cap and its forced-wide twin."""
+    api = gpu_lib
+    if wide:
+        monkeypatch.setenv("KAIJU_GPU_FORCE_WIDE", wide)
+    else:
+        monkeypatch.delenv("KAIJU_GPU_FORCE_WIDE", raising=False)
+    idx = api.Index(golden.fmi)
+    assert bool(idx.layout().wide) == bool(wide)
+    for seqs, off, pe in ((golden.seqs, golden.off, False), (golden.pseqs, golden.poff, True)):
+        clf = api.Classifier(idx, api.default_params("mem", seg=1))
+        plain = clf.classify(seqs, off, paired=pe).copy()
+        assert clf.stats().error_flags == 0 and plain["n_ids"].any()
+        clf.count_ops(True)
+        counting = clf.classify(seqs, off, paired=pe).copy()
+        assert sum(clf.op_counts().values()) > 0                   # (the counting instantiation ran)
+        clf.count_ops(False)
+        verbose = clf.classify_verbose(seqs, off, paired=pe)[0]
+        for f in ("best", "n_ids", "flags", "taxid"):
+            assert (counting[f] == plain[f]).all(), (wide, pe, "counting", f)
+            assert (verbose[f] == plain[f]).all(), (wide, pe, "-v", f)

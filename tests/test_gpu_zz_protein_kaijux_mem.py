@@ -113,6 +113,12 @@ def test_cli_kaijux_mem(gpu_lib, golden, tmp_path):
             assert open(out).read() == open(ref).read(), (pe, v)
 
 
+def test_kaijux_mem_order_forced_wide(gpu_lib, oracle, tmp_path, monkeypatch):
+    """the same through the lane with 64-bit positions (k_mem_wide2_x)"""
+    monkeypatch.setenv("KAIJU_GPU_FORCE_WIDE", "17")
+    test_kaijux_mem_order_under_the_id_cap(gpu_lib, oracle, tmp_path)
+
+
 def test_kaijux_mem_order_under_the_id_cap(gpu_lib, oracle, tmp_path):
     """a database of near-identical sequences: every match interval holds more rows than the 21-id cap lets through, so the
     collected sequences depend on the order in which the matches of a fragment are visited; == the oracle's kaijux mode

@@ -1,4 +1,5 @@
-"""register / scratch / LDS use of every kernel of capi.hip (or of --src FILE, a name in kaiju_amd/csrc or a path) as the
+"""register / scratch / LDS use of every kernel of capi.hip (or of --src FILE, a name in kaiju_amd/csrc or a path: capi_index.hip
+   holds the kernels of the index load, exact_pass.hip those of the exact pass, capi_text.hip none) as the
    compiler reports it (gfx950 cross-compile, no GPU needed)
    python tests/tools/kres.py [extra -D flags ...] [--filter REGEX] [--src FILE]"""
 import os
