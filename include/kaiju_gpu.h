@@ -28,6 +28,8 @@
  *   kaiju_gpu_lca_batch_device  the same on the device (kaiju_gpu_taxonomy_upload: the tree in HBM)
  *   kaiju_finalize_hits         E-value gate ConsumerThread.cpp:500-513, LCA call :538,:625 and the
  *                               C/U decision :724-739
+ *   kaiju_gpu_merge_text        the loop of kaiju-mergeOutputs.cpp:110-295, calc_lca :355-399 and
+ *                               is_ancestor util.cpp:42-77 on the device
  */
 #ifndef KAIJU_GPU_H
 #define KAIJU_GPU_H
@@ -589,6 +591,70 @@ int kaiju_gpu_annotate_text(kaiju_gpu_annotator *a, const char *text, uint64_t b
 /* Host only: an out_cap that cannot overflow for a text of n_lines lines (its '\n' bytes plus one):
    bytes + 1 + n_lines * (1 + max_annotation) */
 uint64_t kaiju_gpu_annotate_bound(uint64_t bytes, uint64_t n_lines, const kaiju_gpu_taxon_names *names);
+
+/* ---- kaiju-mergeOutputs on two output texts: lines of two runs in, merged lines out --------------------------- */
+/* Line k of text 1 and line k of text 2 - two classifications of the same reads, sorted alike - give line k of the output
+   (kaiju_amd/csrc/merge.hip; the rules: kj_merge.h, those of kaiju-mergeOutputs.cpp:110-295, :355-399 and util.cpp:42-77):
+     - U,U: "U\t<name>\t0\n".  C,U / U,C: "C\t<name>\t<id>[\t<score>]\n" of the classified side.  C,C: equal id texts give id1
+       and the score text of the larger value; different score values give the id and score of the larger one; else score1
+       and, by `conflict`, id1, id2, the tool's own LCA printed as a number, or the lower of the two in one lineage
+     - with use_score (the tool's -s) a 'C' line needs a fourth column; the id is then every byte of the third
+     - the first pair that fails (KAIJU_GPU_MERGE_STOP_*) ends the run: the pairs in front of it are written, nothing else
+     - scores are compared as decimals.  A C,C pair with a score of more than 15 significant digits, or outside
+       [1e-300, 1e300) and below 1e309, stops the run with KAIJU_GPU_MERGE_STOP_SCORE_WIDE rather than guess what the
+       comparison of the doubles would give
+   The merger is scratch on the device of `tax`; it needs no index and no context.  One call at a time per merger. */
+enum { KAIJU_GPU_MERGE_FIRST = 0, KAIJU_GPU_MERGE_SECOND = 1, KAIJU_GPU_MERGE_LCA = 2, KAIJU_GPU_MERGE_LOWEST = 3 };   /* -c 1, 2, lca, lowest */
+enum {
+  KAIJU_GPU_MERGE_STOP_NONE = 0,
+  KAIJU_GPU_MERGE_STOP_1_CLASS = 1,    /* line of text 1: byte 0 is neither 'C' nor 'U' (an empty line too)                */
+  KAIJU_GPU_MERGE_STOP_1_TABS = 2,     /* ... fewer than two tabs                                                          */
+  KAIJU_GPU_MERGE_STOP_1_COLUMN = 3,   /* ... nothing behind tab 2; with use_score on a 'C' line: no tab 3, nothing behind it */
+  KAIJU_GPU_MERGE_STOP_2_SHORT = 4,    /* text 2 has no such line (final only)                                             */
+  KAIJU_GPU_MERGE_STOP_2_CLASS = 5,    /* the three above for the line of text 2                                           */
+  KAIJU_GPU_MERGE_STOP_2_TABS = 6,
+  KAIJU_GPU_MERGE_STOP_2_COLUMN = 7,
+  KAIJU_GPU_MERGE_STOP_NAMES = 8,      /* the names differ                                                                 */
+  KAIJU_GPU_MERGE_STOP_SCORE_WIDE = 9  /* a score outside what the device compares exactly                                 */
+};
+typedef struct kaiju_gpu_merger kaiju_gpu_merger;
+/* tax == NULL: the empty tree (device_id says where the merger lives; with a tree it must be the tree's device).
+   KAIJU_GPU_MERGE_LCA without a tree is KAIJU_GPU_ERR_ARG, as the tool refuses -c lca without -t */
+int kaiju_gpu_merger_create(const kaiju_gpu_taxonomy *tax, int device_id, int conflict, int use_score, kaiju_gpu_merger **out);
+void kaiju_gpu_merger_free(kaiju_gpu_merger *m);
+typedef struct kaiju_gpu_merge_info {
+  uint64_t text_bytes;             /* size of the whole merged text, also when it overflowed                               */
+  uint64_t used1, used2;           /* bytes of text 1 / 2 in the lines that were paired; the caller carries the rest       */
+  uint64_t n_pairs;                /* the smaller of the two line counts                                                   */
+  uint64_t count;                  /* lines of text 1 read: the pairs written and the one that stopped (the tool's -v)     */
+  uint64_t count_c1, count_c2;     /* written pairs classified in text 1 / in text 2                                       */
+  uint64_t count_c12, count_c3;    /* ... in both / in either                                                              */
+  uint64_t count_c1_not_c2, count_c2_not_c1;
+  uint64_t stop_pair;              /* index of the pair that stopped the run; all ones: none                               */
+  uint32_t stop_why;               /* KAIJU_GPU_MERGE_STOP_*                                                               */
+  uint32_t more_in_2;              /* final, no stop: text 2 has a further line and it is not empty (the tool warns)       */
+  uint32_t overflow;
+  uint32_t reserved;
+} kaiju_gpu_merge_info;            /* 112 bytes */
+/* All pointers device pointers; every pass is queued on `stream` and nothing synchronises, so d_text1 / d_text2 may be the
+   d_out of two formatter calls queued on the same stream in front of it.  The three buffers are 16-byte aligned and the texts
+   readable up to the next multiple of 16 behind their bytes (KAIJU_GPU_ERR_ARG otherwise, as for bytes of 2^32 - 16 and more
+   and for buffers on another device).  final == 0: only lines a '\n' ends count, n_pairs of them are merged and used1 / used2
+   say where the rest starts.  final != 0: a last line without '\n' is a line, more lines in text 1 stop the run, more in text 2
+   set more_in_2.  Lines are written whole or not at all, no byte at or behind out_cap is touched.  The scratch - 4 bytes per
+   byte of either text and 12 per byte of the shorter one - lives in the merger. */
+int kaiju_gpu_merge_text_device(kaiju_gpu_merger *m, const void *d_text1, uint64_t bytes1, const void *d_text2, uint64_t bytes2,
+                                int final, void *d_out, uint64_t out_cap, kaiju_gpu_merge_info *d_info, void *stream);
+/* The same for host memory (no alignment asked for): upload, the passes, the download of the lines written */
+int kaiju_gpu_merge_text(kaiju_gpu_merger *m, const char *text1, uint64_t bytes1, const char *text2, uint64_t bytes2, int final,
+                         char *out, uint64_t out_cap, kaiju_gpu_merge_info *info);
+/* Host only: an out_cap that cannot overflow: bytes1 + bytes2 + 2 + 20 * (min(bytes1, bytes2) / 4 + 2) */
+uint64_t kaiju_gpu_merge_bound(uint64_t bytes1, uint64_t bytes2);
+/* Diagnostics.  A merger created with KAIJU_GPU_MERGE_TIMES=1 in the environment records a HIP event between the passes of
+   every call (KAIJU_GPU_ERR_UNSUPPORTED otherwise): the milliseconds of the last call's passes - lines and plan, pair, count,
+   offsets, write, finish - into ms[0 .. n), n <= KAIJU_GPU_MERGE_PASSES.  Waits for that call. */
+enum { KAIJU_GPU_MERGE_PASSES = 6 };
+int kaiju_gpu_merge_pass_ms(kaiju_gpu_merger *m, float *ms, uint32_t n);
 
 /* ---- the lines of kaiju -v on the device: hits and matches in, text out ------------------------------------ */
 /* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi WITH -v, as HIP passes

@@ -84,6 +84,13 @@ ANNOTATE_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_lines", "<u4"), ("n_c
                                 ("n_unknown_taxon", "<u4"), ("n_unnamed_taxon", "<u4"), ("n_dropped", "<u4"), ("n_empty", "<u4"), ("overflow", "<u4"),
                                 ("reserved", "<u4")])
 assert ANNOTATE_INFO_DTYPE.itemsize == 48
+MERGE_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("used1", "<u8"), ("used2", "<u8"), ("n_pairs", "<u8"), ("count", "<u8"), ("count_c1", "<u8"),
+                             ("count_c2", "<u8"), ("count_c12", "<u8"), ("count_c3", "<u8"), ("count_c1_not_c2", "<u8"), ("count_c2_not_c1", "<u8"),
+                             ("stop_pair", "<u8"), ("stop_why", "<u4"), ("more_in_2", "<u4"), ("overflow", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_merge_info
+assert MERGE_INFO_DTYPE.itemsize == 112
+MERGE_FIRST, MERGE_SECOND, MERGE_LCA, MERGE_LOWEST = 0, 1, 2, 3
+MERGE_MODES = {"1": MERGE_FIRST, "2": MERGE_SECOND, "lca": MERGE_LCA, "lowest": MERGE_LOWEST}
+MERGE_STOP_SCORE_WIDE = 9
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -211,6 +218,14 @@ def lib():
         L.kaiju_gpu_annotate_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_annotate_bound.restype = C.c_uint64
         L.kaiju_gpu_annotate_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+    if hasattr(L, "kaiju_gpu_merger_create"):                 # (likewise)
+        L.kaiju_gpu_merger_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.kaiju_gpu_merger_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_merge_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                  C.c_void_p]
+        L.kaiju_gpu_merge_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_merge_bound.restype = C.c_uint64
+        L.kaiju_gpu_merge_bound.argtypes = [C.c_uint64, C.c_uint64]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -531,6 +546,63 @@ class Annotator:
     def close(self):
         if self._h:
             lib().kaiju_gpu_annotator_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Merger:
+    """kaiju-mergeOutputs on a device (kaiju_gpu_merger_create): two texts of output lines in, the merged text out.  ``dtax``: the
+    tree of -t (None: the empty tree, which ``conflict="lca"`` refuses); ``conflict``: "1", "2", "lca" or "lowest" (-c);
+    ``use_score``: -s.  It needs no index and no Classifier."""
+
+    def __init__(self, dtax: DeviceTaxonomy | None = None, conflict="lca", use_score=False, device: int = 0):
+        if not hasattr(lib(), "kaiju_gpu_merger_create"):
+            raise KaijuGpuError("this library was linked without merge.hip")
+        self._tax = dtax                                      # (the tree must outlive the merger)
+        self._h = C.c_void_p()
+        code = MERGE_MODES[conflict] if isinstance(conflict, str) else int(conflict)
+        _check(lib().kaiju_gpu_merger_create(dtax._h if dtax is not None else None, device, code, 1 if use_score else 0, C.byref(self._h)))
+
+    @staticmethod
+    def bound(text1, text2) -> int:
+        return int(lib().kaiju_gpu_merge_bound(len(text1), len(text2)))
+
+    def merge(self, text1, text2, final=True, out_cap=None, out=None):
+        """Returns (bytes, info): the merged lines and a MERGE_INFO_DTYPE record.  final=False: only lines a newline ends are
+        paired and info["used1"] / info["used2"] say where the rest starts.  out_cap: the capacity (default: one that cannot
+        overflow); when the text overflows it, info["overflow"] is set and only whole lines in front of it are written.  out: a
+        uint8 array of at least out_cap bytes to write into - the lines written change, nothing else does -; the first value
+        returned is then None"""
+        text1, text2 = bytes(text1), bytes(text2)
+        cap = int(out_cap) if out_cap is not None else self.bound(text1, text2)
+        own = out is None
+        if own:
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.size >= cap
+        info = np.zeros(1, dtype=MERGE_INFO_DTYPE)
+        _check(lib().kaiju_gpu_merge_text(self._h, text1, len(text1), text2, len(text2), 1 if final else 0, out.ctypes.data, cap, info.ctypes.data))
+        if not own:
+            return None, info[0]
+        written = min(int(info[0]["text_bytes"]), cap)
+        if info[0]["overflow"]:                               # (the buffer was zeroed: behind the last line written lies no newline)
+            written = bytes(out[:written]).rfind(b"\n") + 1
+        return bytes(out[:written]), info[0]
+
+    def merge_device(self, d_text1_ptr: int, nbytes1: int, d_text2_ptr: int, nbytes2: int, d_out_ptr: int, out_cap: int, d_info_ptr: int, final=True,
+                     stream: int = 0):
+        """the same for device-resident buffers (raw pointers, all 16-byte aligned): kaiju_gpu_merge_text_device, asynchronous
+        on ``stream``"""
+        _check(lib().kaiju_gpu_merge_text_device(self._h, d_text1_ptr or None, nbytes1, d_text2_ptr or None, nbytes2, 1 if final else 0, d_out_ptr or None,
+                                                 out_cap, d_info_ptr or None, stream or None))
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_merger_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
