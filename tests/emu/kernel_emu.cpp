@@ -33,6 +33,16 @@ struct EmuIndex {
   bool xmode = false;         // ids are sequence numbers (kaijux)
 };
 
+// the pattern every working array of emu_classify starts with (emu_set_fill below); empty: zeros
+static std::vector<uint8_t> g_fill;
+template <class T> static void emu_fill(T *p, size_t count) {
+  if (g_fill.empty() || !count) return;
+  uint8_t *b = reinterpret_cast<uint8_t *>(p);
+  const size_t nb = count * sizeof(T), fl = g_fill.size();
+  for (size_t x = 0; x < nb; x++) b[x] = g_fill[x % fl];
+}
+template <class V> static void emu_fill(V &v) { emu_fill(v.data(), v.size()); }
+
 extern "C" {
 
 static void *emu_index_load_mode(const char *path, char *err, int errlen, bool xmode) {
@@ -276,6 +286,50 @@ const char *emu_seq_name(void *h, uint32_t iseq) {
 }
 const char *emu_alphabet(void *h) { return ((EmuIndex *)h)->packed.alphabet.c_str(); }
 
+// ---- what the working memory of the next emu_classify calls holds before the lanes run --------------------------------------
+// A context of the product keeps its buffers between calls and clears few of them; here every call allocates its own, zeroed
+// by default.  emu_set_fill(pattern, len): every working array of emu_classify (peptide area, fragment lists, read
+// descriptors, SEG work list and records, the scratch of the lanes, of the retry pass and of the exact pass) starts as the
+// pattern repeated; len == 0: zeros again.  tests/test_call_history_emu.py
+void emu_set_fill(const uint8_t *pattern, uint32_t len) { g_fill.assign(pattern, pattern + len); }
+// emu_set_hits(recs, n), n > 0: the next calls ask for the 16-byte records as kaiju_gpu_classify_batch_device_compact does
+// (FlowCall::records16); where the plan then leaves the hit records uncleared (FlowPlan::clear_out == false) record r starts as
+// recs[r % n] - what an earlier call left in the caller's buffer.  n == 0: off.  emu_last_clear_out(): the last plan's clear_out
+static std::vector<Hit> g_hits_before;
+static int g_last_clear_out = -1;
+void emu_set_hits(const kaiju_gpu_hit *recs, uint32_t n) {
+  g_hits_before.resize(n);
+  if (n) memcpy(g_hits_before.data(), recs, sizeof(Hit) * n);
+}
+int emu_last_clear_out() { return g_last_clear_out; }
+// ... and its stage 1 (kj_flow.h: FlowStage1 - 0 Protein, 1 Old, 2 Fast, 3 FastTrig, 4 Long, 5 LongTrig, 6 Team)
+static int g_last_stage1 = -1;
+int emu_last_stage1() { return g_last_stage1; }
+// the peptide area as the last emu_classify call left it: up to n bytes from `offset` into out; returns how many there were
+static std::vector<uint8_t> g_last_pep;
+uint32_t emu_pep_read(uint64_t offset, uint8_t *out, uint32_t n) {
+  if (offset >= g_last_pep.size()) return 0;
+  const uint32_t k = (uint32_t)std::min<uint64_t>(n, g_last_pep.size() - offset);
+  memcpy(out, g_last_pep.data() + offset, k);
+  return k;
+}
+// emu_set_carry(1): the peptide area of the next calls starts as the last call left it (as far as that reaches; the fill
+// pattern behind it) - what a context's buffer is to the second of two calls
+static int g_carry = 0;
+void emu_set_carry(int on) { g_carry = on; }
+// ... and where the fragments of read r lay in it: *pep = the offset of the read's peptide area, (start, len) of up to cap
+// fragments into start_len; returns the number of fragments the read had
+static std::vector<ReadMeta> g_last_meta;
+static std::vector<Frag> g_last_frags;
+uint32_t emu_frags_read(uint32_t r, uint64_t *pep, uint32_t *start_len, uint32_t cap) {
+  if (r >= g_last_meta.size()) return 0;
+  const ReadMeta &m = g_last_meta[r];
+  const uint32_t nf = m.nfrag & ~kNfragSegPending;
+  *pep = m.pep;
+  for (uint32_t k = 0; k < nf && k < cap; k++) { start_len[2 * k] = g_last_frags[m.frag + k].start; start_len[2 * k + 1] = g_last_frags[m.frag + k].len; }
+  return nf;
+}
+
 // The product's flow plan (kj_flow.h: plan_flow) as plain integers, for tests/test_flow_plan.py.
 //   ix[7]   blocks64, kline, kline_k, kmer64, kmer_k, wide, row_tax
 //   sw[17]  mode, m, seed_length, seg, Params::flags (kParamXOrder | kParamProtein), verbose, verbose_v1, mem_v1, stage1_old,
@@ -329,7 +383,9 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   sw.mem_v1 = lane_env != nullptr; sw.greedy2 = p.mode == 1 && flow_greedy2(fi, p.seed_length) && !lane_env;
   sw.stage1_old = getenv("KAIJU_EMU_STAGE1_OLD") != nullptr; sw.lazy_seg = !getenv("KAIJU_EMU_LAZY_OFF");
   sw.blocks_retry = p.mode == 0 ? 16 : 4;                   // (as kaiju_gpu_create; the one lane here has no use for them)
-  const FlowPlan plan = plan_flow(fi, sw, FlowCall{n, paired != 0, maxlen ? maxlen : 1, n ? off[2 * (uint64_t)n] : 0, false});
+  const FlowPlan plan = plan_flow(fi, sw, FlowCall{n, paired != 0, maxlen ? maxlen : 1, n ? off[2 * (uint64_t)n] : 0, !g_hits_before.empty()});
+  g_last_clear_out = plan.clear_out ? 1 : 0;
+  g_last_stage1 = (int)plan.stage1;
   if (plan.status == FlowStatus::ProteinPaired) return KAIJU_GPU_ERR_ARG;
   if (plan.status != FlowStatus::Ok) return KAIJU_GPU_ERR_UNSUPPORTED;
   const bool lazy = plan.seg == FlowSeg::Lazy;
@@ -342,6 +398,10 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   std::vector<ReadMeta> meta(n);
   std::vector<Hit> hits(n);
   memset(hits.data(), 0, sizeof(Hit) * n);
+  // (the product: d_out is zeroed where the plan says so and is the caller's memory as it stands otherwise)
+  if (!plan.clear_out && !g_hits_before.empty()) for (uint32_t r = 0; r < n; r++) hits[r] = g_hits_before[r % g_hits_before.size()];
+  emu_fill(pep); emu_fill(frags); emu_fill(meta);
+  if (g_carry && !g_last_pep.empty()) memcpy(pep.data(), g_last_pep.data(), std::min(pep.size(), g_last_pep.size()));
   b.pep = pep.data(); b.frags = frags.data(); b.meta = meta.data(); b.hits = hits.data();
   uint32_t err = 0;
   // stage 1 -> SEG pass -> (MEM) apply
@@ -349,10 +409,12 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   const uint32_t seg_cap = (uint32_t)(frags.size() / 2 + 8);
   std::vector<SegWork> seg_items(seg_cap);
   std::vector<SegRec> seg_recs(seg_cap);
+  emu_fill(seg_items); emu_fill(seg_recs);
   SegQueue sq{seg_items.data(), seg_recs.data(), &seg_count, seg_cap};
   const SegCtx cx = seg_ctx(ix->st, ix->st.ent_g, ix->st.lnfact);
   // peptides are staged (here: linear scratch) and copied out, as the kernel does with its LDS area
   std::vector<uint8_t> stage((size_t)4 * maxlen + 256);
+  emu_fill(stage);
   const bool staged = !getenv("KAIJU_EMU_NOSTAGE");
   Stage1Tables s1tab;
   build_stage1_tables(ix->ct, ix->st, s1tab);
@@ -390,6 +452,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
     int32_t segwork[4 * kSegMaxRegions];
     std::vector<uint8_t> segstage(64);   // small on purpose: exercises both the staged and the direct path
     std::vector<uint8_t> segcls(64);
+    emu_fill(segwork, 4 * kSegMaxRegions); emu_fill(segstage); emu_fill(segcls);
     for (uint32_t s = 0; s < seg_count && s < seg_cap; s++)
       seg_compute(cx, emu_coop(), b, p, sq, s, segstage.data(), (uint32_t)segstage.size(), segwork, segcls.data(), [] {});
     if (plan.seg_apply) for (uint32_t r = 0; r < n; r++) seg_apply_mem(ix->ct, p, b, sq, r, &err);
@@ -422,6 +485,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   std::vector<uint16_t> ord(pool_cap);
   std::vector<GMatch> matches(match_cap);
   std::vector<GBest> bestv(64);
+  emu_fill(retry); emu_fill(win, kWin); emu_fill(si); emu_fill(pool); emu_fill(ord); emu_fill(matches); emu_fill(bestv);
   for (int pass = 0; pass < 2; pass++) {
     WorkList wl;
     wl.counter = &counter;
@@ -438,6 +502,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       si.assign(2 * (size_t)maxlen + 64, SIEntry{});
       pool.assign(65535, GItem{}); ord.assign(65535, 0);
       matches.assign((size_t)maxlen + 8, GMatch{});
+      emu_fill(si); emu_fill(pool); emu_fill(ord); emu_fill(matches);
     }
     if (p.mode == 0) {
       LaneScratch ls{si.data(), (uint32_t)si.size(), win};
@@ -498,6 +563,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
           }
           int32_t segwork[4 * kSegMaxRegions];
           std::vector<uint8_t> segstage(64), segcls(64);
+          emu_fill(segwork, 4 * kSegMaxRegions); emu_fill(segstage); emu_fill(segcls);
           for (uint32_t s2 = 0; s2 < seg_count && s2 < seg_cap; s2++)
             seg_compute(cx, emu_coop(), b, p, sq, s2, segstage.data(), (uint32_t)segstage.size(), segwork, segcls.data(), [] {});
           for (uint32_t r : seglist) seg_apply_mem(ix->ct, p, b, sq, r, &err);
@@ -517,6 +583,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       gs.matches = matches.data(); gs.match_cap = (uint32_t)matches.size();
       gs.best = bestv.data(); gs.win = win;
       std::vector<GBestV> bestvv(64);
+      emu_fill(bestvv);
       gs.bestv = g_vb.n_acc ? bestvv.data() : nullptr;
       if (plan.lane != FlowLane::GreedyV1 && pass == 0) {
         alignas(16) uint32_t lds_win[kGWinStride], lds_mq[kGMqStride], lds_prio[kGPrioStride];
@@ -529,6 +596,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
         std::vector<uint16_t> mq_ext(kGMaxMAll - kGMaxM, 0xdead);
         std::vector<GBest2> best2(64);
         std::vector<GBest2W> best2w(64);
+        emu_fill(pool2); emu_fill(matches2); emu_fill(best2); emu_fill(best2w);
         const char *ge = getenv("KAIJU_EMU_GATE");
         GreedyScratch2 g2{reinterpret_cast<uint8_t *>(lds_win), reinterpret_cast<uint16_t *>(lds_mq), lds_prio, pool2.data(),
                           prio_ext.data(), matches2.data(), mq_ext.data(), best2.data(), best2w.data(), ge ? (uint32_t)atoi(ge) : 3u};
@@ -541,6 +609,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
         //  -DKJ_GREEDY3 builds with KAIJU_GPU_GREEDY_LANE=v3)
         const char *g3e = getenv("KAIJU_EMU_GREEDY");
         std::vector<GBestV> bestv2(64);
+        emu_fill(bestv2);
         if (lane_vb) { g2.bestv = bestv2.data(); g2.vb = g_vb; g2.lane = 0; }      // (k_greedy2_vb / k_greedy2_wide_vb)
         if (lane_vb && lane_wide) greedy_lane2<false, true, true>(d, ix->ct, pg, sq, b, wl, g2);
         else if (lane_vb) greedy_lane2<false, false, true>(d, ix->ct, pg, sq, b, wl, g2);
@@ -605,6 +674,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       std::vector<SegWork> items2(cap2);
       std::vector<uint2> index2(cap2);
       std::vector<int32_t> pool2((size_t)2 * pool_cap + 2);
+      emu_fill(items2); emu_fill(index2); emu_fill(pool2);
       SegQueue sq2{items2.data(), nullptr, &count2, cap2};
       BigSeg big{index2.data(), pool2.data(), &pairs, pool_cap};
       uint8_t code[256];
@@ -619,6 +689,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       const int cap_ints = (int)(2 * max_frag + 4);
       std::vector<int32_t> work2((size_t)4 * cap_ints);
       std::vector<uint8_t> cls2((size_t)max_frag + 64);
+      emu_fill(work2); emu_fill(cls2);
       for (uint32_t s2 = 0; s2 < count2 && s2 < cap2; s2++)
         seg_compute_big(cx, emu_coop(), b, sq2, big, s2, work2.data(), cap_ints, cls2.data(), &err, [] {});
       if (p.mode == 0) for (uint32_t r : redo) seg_apply_mem_big(ix->ct, p, b, big, r);
@@ -630,6 +701,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
       si.assign(2 * (size_t)maxlen + 64, SIEntry{});
       pool.assign(65535, GItem{}); ord.assign(65535, 0);
       matches.assign((size_t)maxlen + 8, GMatch{});
+      emu_fill(si); emu_fill(pool); emu_fill(ord); emu_fill(matches);
       if (p.mode == 0) {
         LaneScratch ls{si.data(), (uint32_t)si.size(), win};
         mem_lane<uint64_t>(d, p, b, wl, ls, g_vb);
@@ -639,6 +711,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
         gs.matches = matches.data(); gs.match_cap = (uint32_t)matches.size();
         gs.best = bestv.data(); gs.win = win;
         std::vector<GBestV> bestvv(64);
+        emu_fill(bestvv);
         gs.bestv = g_vb.n_acc ? bestvv.data() : nullptr;
         greedy_lane(d, ix->ct, p, sq2, b, wl, gs, g_vb, &big);
       }
@@ -646,6 +719,7 @@ int emu_classify(void *h, const kaiju_gpu_params *gp, const char *seqs, const ui
   }
   static_assert(sizeof(Hit) == sizeof(kaiju_gpu_hit), "hit layout");
   memcpy(out, hits.data(), sizeof(Hit) * n);
+  g_last_pep = pep; g_last_meta = meta; g_last_frags = frags;
   return err ? -100 : 0;
 }
 

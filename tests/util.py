@@ -67,6 +67,43 @@ class Emu:
                                    C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                    C.c_char_p, C.c_uint64]
 
+        E.emu_set_fill.argtypes = [C.c_void_p, C.c_uint32]
+        E.emu_set_hits.argtypes = [C.c_void_p, C.c_uint32]
+        E.emu_pep_read.restype = C.c_uint32
+        E.emu_pep_read.argtypes = [C.c_uint64, C.c_void_p, C.c_uint32]
+        E.emu_frags_read.restype = C.c_uint32
+        E.emu_frags_read.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32]
+
+    def set_fill(self, pattern: bytes = b""):
+        """what every working array of the next classify calls holds before the lanes run (b"": zeros)"""
+        self.lib.emu_set_fill(C.cast(C.c_char_p(pattern), C.c_void_p), len(pattern))
+
+    def set_hits(self, recs=None):
+        """the next classify calls ask for the 16-byte records too; where the plan then leaves the hit records uncleared,
+        record r starts as recs[r % len(recs)] (None: off)"""
+        if recs is None or len(recs) == 0:
+            self.lib.emu_set_hits(None, 0)
+        else:
+            recs = np.ascontiguousarray(recs, dtype=GPU_HIT)
+            self.lib.emu_set_hits(recs.ctypes.data, len(recs))
+
+    def set_carry(self, on: bool):
+        """the peptide area of the next classify calls starts as the last call left it (a context's buffer between two calls)"""
+        self.lib.emu_set_carry(1 if on else 0)
+
+    def pep_read(self, offset, n):
+        """n bytes of the peptide area of the last classify call from `offset` (fewer at its end)"""
+        out = np.zeros(n, dtype=np.uint8)
+        k = self.lib.emu_pep_read(offset, out.ctypes.data, n)
+        return out[:k]
+
+    def frags_read(self, r, cap=256):
+        """(offset of read r's peptide area, [(start, len) of its fragments]) as the last classify call left them"""
+        pep = C.c_uint64(0)
+        sl = np.zeros(2 * cap, dtype=np.uint32)
+        nf = self.lib.emu_frags_read(r, C.byref(pep), sl.ctypes.data, cap)
+        return pep.value, [(int(sl[2 * k]), int(sl[2 * k + 1])) for k in range(min(nf, cap))]
+
     def load(self, fmi):
         err = C.create_string_buffer(512)
         h = self.lib.emu_index_load(fmi.encode(), err, 512)
