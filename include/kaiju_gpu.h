@@ -656,6 +656,67 @@ uint64_t kaiju_gpu_merge_bound(uint64_t bytes1, uint64_t bytes2);
 enum { KAIJU_GPU_MERGE_PASSES = 6 };
 int kaiju_gpu_merge_pass_ms(kaiju_gpu_merger *m, float *ms, uint32_t n);
 
+/* ---- kaiju2table on output texts: lines in, reads per taxon out ------------------------------------------------ */
+/* What kaiju2table.cpp:192-236 keeps per input file, kept per slot of the tree of `names` on its device
+   (kaiju_amd/csrc/tally.hip; the rules: kj_tally.h):
+     - every line that is not empty counts in n_total; byte 0 not 'C': n_unclassified
+     - the id is the run of digits behind the second tab.  None, or a value above 2^64 - 1: n_bad_id.  No node of nodes.dmp:
+       n_unknown_taxon.  Else the node's direct count rises, and n_virus when the node is 10239 or below it
+     - at kaiju_gpu_tally_result a node's reads count for itself and for every ancestor but a node that is its own parent;
+       those of a node at or below 10239 count for that node alone
+   Texts are added in as many calls as the caller likes; nothing reaches the host before kaiju_gpu_tally_result.  `names` may
+   be of any mode (only its keys and parents are read) and must outlive the tally.  One call at a time per tally; calls on
+   different streams are ordered by an event of the tally. */
+typedef struct kaiju_gpu_tally kaiju_gpu_tally;
+int kaiju_gpu_tally_create(const kaiju_gpu_taxon_names *names, kaiju_gpu_tally **out);
+void kaiju_gpu_tally_free(kaiju_gpu_tally *t);
+/* every count back to 0 (a new input file) */
+int kaiju_gpu_tally_reset(kaiju_gpu_tally *t);
+typedef struct kaiju_gpu_tally_info {
+  uint64_t used;                   /* bytes of the text in the lines that were counted; the caller carries the rest        */
+  uint64_t n_lines;                /* lines looked at, empty ones included                                                 */
+  uint64_t n_total, n_unclassified, n_bad_id, n_unknown_taxon, n_virus;
+} kaiju_gpu_tally_info;            /* 56 bytes */
+/* All pointers device pointers; every pass is queued on `stream` and nothing synchronises, so d_text may be the d_out of a
+   formatter call queued on the same stream in front of it.  d_text is 16-byte aligned and readable up to the next multiple
+   of 16 behind its bytes (KAIJU_GPU_ERR_ARG otherwise, as for bytes of 2^32 - 16 and more and for a buffer on another device).
+   final == 0: only lines a '\n' ends count and `used` says where the rest starts.  final != 0: a last line without '\n' is
+   a line.  *d_info describes this call alone.  The scratch - 4 bytes per byte of the text - lives in the tally. */
+int kaiju_gpu_tally_add_text_device(kaiju_gpu_tally *t, const void *d_text, uint64_t bytes, int final, kaiju_gpu_tally_info *d_info,
+                                    void *stream);
+/* The same for host memory (no alignment asked for): upload, the passes, the info */
+int kaiju_gpu_tally_add_text(kaiju_gpu_tally *t, const char *text, uint64_t bytes, int final, kaiju_gpu_tally_info *info);
+typedef struct kaiju_gpu_tally_entry {
+  uint64_t taxon, direct, summed;  /* reads of the node itself / of what counts for it (> 0)                               */
+  uint32_t virus, reserved;        /* 1: the node is 10239 or below it                                                     */
+} kaiju_gpu_tally_entry;           /* 32 bytes */
+/* Everything since the last reset: the nodes with summed > 0 in a fixed order (that of their slots) into entries[0 .. cap),
+   their number into *n_entries, the sums of the infos into *totals (`used`: the sum too).  More than cap nodes:
+   KAIJU_GPU_ERR_ARG with *n_entries set and no entry written.  Waits for the calls before it; the counts stay. */
+int kaiju_gpu_tally_result(kaiju_gpu_tally *t, kaiju_gpu_tally_entry *entries, uint64_t cap, uint64_t *n_entries, kaiju_gpu_tally_info *totals);
+/* Diagnostics.  A tally created with KAIJU_GPU_TALLY_TIMES=1 in the environment records a HIP event between the passes of
+   every add call (KAIJU_GPU_ERR_UNSUPPORTED otherwise): the milliseconds of the last call's passes - lines, count, finish -
+   into ms[0 .. n), n <= KAIJU_GPU_TALLY_PASSES.  Waits for that call. */
+enum { KAIJU_GPU_TALLY_PASSES = 3 };
+int kaiju_gpu_tally_pass_ms(kaiju_gpu_tally *t, float *ms, uint32_t n);
+
+/* ---- the rows of kaiju2table (host only, no GPU) -------------------------------------------------------------- */
+enum { KAIJU_TABLE_EXPAND_VIRUSES = 1, KAIJU_TABLE_FILTER_UNCLASSIFIED = 2, KAIJU_TABLE_FULL_PATH = 4 };   /* -e, -u, -p */
+typedef struct kaiju_table_options {
+  const char *rank;                /* -r: phylum, class, order, family, genus or species                                   */
+  const char *ranks_csv;           /* -l, NULL: none.  Not together with KAIJU_TABLE_FULL_PATH; it must hold `rank`         */
+  float min_percent;               /* -m, in [0, 100]; not together with min_count                                         */
+  int32_t min_count;               /* -c, >= 0                                                                             */
+  uint32_t flags;                  /* KAIJU_TABLE_*                                                                        */
+  uint32_t reserved;
+} kaiju_table_options;
+/* The rows that kaiju2table.cpp:238-360 prints for one input file - no header row - from the entries and totals of
+   kaiju_gpu_tally_result (in any order; `names` of any mode), `label` in the file column.  Returns KAIJU_GPU_OK with the size
+   of the whole text in *n_bytes and its first min(size, cap) bytes in buf, or KAIJU_GPU_ERR_ARG for options the tool refuses. */
+int kaiju_table_rows(const kaiju_taxon_names *names, const kaiju_gpu_tally_entry *entries, uint64_t n_entries,
+                     const kaiju_gpu_tally_info *totals, const kaiju_table_options *opt, const char *label, char *buf, uint64_t cap,
+                     uint64_t *n_bytes);
+
 /* ---- the lines of kaiju -v on the device: hits and matches in, text out ------------------------------------ */
 /* What stage 4 of the command line programs does on the host for kaiju / kaiju-multi WITH -v, as HIP passes
    (kaiju_amd/csrc/format_verbose.hip; the rules: kj_format_verbose.h): the decision of the three-column lines, and for a

@@ -91,6 +91,12 @@ assert MERGE_INFO_DTYPE.itemsize == 112
 MERGE_FIRST, MERGE_SECOND, MERGE_LCA, MERGE_LOWEST = 0, 1, 2, 3
 MERGE_MODES = {"1": MERGE_FIRST, "2": MERGE_SECOND, "lca": MERGE_LCA, "lowest": MERGE_LOWEST}
 MERGE_STOP_SCORE_WIDE = 9
+TALLY_INFO_DTYPE = np.dtype([("used", "<u8"), ("n_lines", "<u8"), ("n_total", "<u8"), ("n_unclassified", "<u8"), ("n_bad_id", "<u8"),
+                             ("n_unknown_taxon", "<u8"), ("n_virus", "<u8")])   # kaiju_gpu_tally_info
+TALLY_ENTRY_DTYPE = np.dtype([("taxon", "<u8"), ("direct", "<u8"), ("summed", "<u8"), ("virus", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_tally_entry
+assert TALLY_INFO_DTYPE.itemsize == 56 and TALLY_ENTRY_DTYPE.itemsize == 32
+TALLY_PASSES = 3
+TABLE_EXPAND_VIRUSES, TABLE_FILTER_UNCLASSIFIED, TABLE_FULL_PATH = 1, 2, 4
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
 
@@ -98,6 +104,11 @@ assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTY
 FORMAT_VERBOSE_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("n_records", "<u4"), ("n_classified", "<u4"), ("overflow", "<u4"),
                                       ("n_inexact", "<u4"), ("n_truncated", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_format_verbose_info
 assert FORMAT_VERBOSE_INFO_DTYPE.itemsize == 32
+
+
+class TableOptions(C.Structure):          # kaiju_table_options
+    _fields_ = [("rank", C.c_char_p), ("ranks_csv", C.c_char_p), ("min_percent", C.c_float), ("min_count", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class KaijuGpuError(RuntimeError):
@@ -226,6 +237,16 @@ def lib():
         L.kaiju_gpu_merge_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_merge_bound.restype = C.c_uint64
         L.kaiju_gpu_merge_bound.argtypes = [C.c_uint64, C.c_uint64]
+    if hasattr(L, "kaiju_gpu_tally_create"):                  # (likewise)
+        L.kaiju_gpu_tally_create.argtypes = [C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_tally_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_tally_reset.argtypes = [C.c_void_p]
+        L.kaiju_gpu_tally_add_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_tally_add_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+        L.kaiju_gpu_tally_result.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_tally_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "kaiju_table_rows"):
+        L.kaiju_table_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TableOptions), C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.kaiju_gpu_seg_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -610,6 +631,86 @@ class Merger:
             self.close()
         except Exception:
             pass
+
+
+class Tally:
+    """kaiju2table's counts on the device of ``dnames`` (kaiju_gpu_tally_create): texts of output lines in, reads per taxon
+    out.  It needs no index and no Classifier; ``dnames`` may be of any mode."""
+
+    def __init__(self, dnames: DeviceTaxonNames):
+        if not hasattr(lib(), "kaiju_gpu_tally_create"):
+            raise KaijuGpuError("this library was linked without tally.hip")
+        self._names = dnames                                  # (the tables must outlive the tally)
+        self._h = C.c_void_p()
+        _check(lib().kaiju_gpu_tally_create(dnames._h, C.byref(self._h)))
+
+    def add(self, text, final=True):
+        """counts the lines of ``text``; final=False: only lines a newline ends, info["used"] says where the rest starts.
+        Returns the TALLY_INFO_DTYPE record of this call"""
+        text = bytes(text)
+        info = np.zeros(1, dtype=TALLY_INFO_DTYPE)
+        _check(lib().kaiju_gpu_tally_add_text(self._h, text, len(text), 1 if final else 0, info.ctypes.data))
+        return info[0]
+
+    def add_device(self, d_text_ptr: int, nbytes: int, d_info_ptr: int, final=True, stream: int = 0):
+        """the same for a device-resident text (raw pointer, 16-byte aligned): kaiju_gpu_tally_add_text_device, asynchronous
+        on ``stream``"""
+        _check(lib().kaiju_gpu_tally_add_text_device(self._h, d_text_ptr or None, nbytes, 1 if final else 0, d_info_ptr or None, stream or None))
+
+    def reset(self):
+        _check(lib().kaiju_gpu_tally_reset(self._h))
+
+    def result(self, cap=None):
+        """(entries, totals) since the last reset: a TALLY_ENTRY_DTYPE array sorted by taxon and a TALLY_INFO_DTYPE record.
+        cap: room for that many entries (default: as many as there are)"""
+        n = C.c_uint64()
+        totals = np.zeros(1, dtype=TALLY_INFO_DTYPE)
+        if cap is None:
+            rc = lib().kaiju_gpu_tally_result(self._h, None, 0, C.byref(n), totals.ctypes.data)
+            if rc == 0:
+                return np.zeros(0, dtype=TALLY_ENTRY_DTYPE), totals[0]
+            cap = n.value
+            if not cap:
+                _check(rc)
+        entries = np.zeros(max(int(cap), 1), dtype=TALLY_ENTRY_DTYPE)
+        _check(lib().kaiju_gpu_tally_result(self._h, entries.ctypes.data, int(cap), C.byref(n), totals.ctypes.data))
+        entries = entries[:n.value]
+        return entries[np.argsort(entries["taxon"], kind="stable")], totals[0]
+
+    def pass_ms(self):
+        """milliseconds of the last add call's passes (lines, count, finish); needs KAIJU_GPU_TALLY_TIMES=1 at creation"""
+        ms = np.zeros(TALLY_PASSES, dtype=np.float32)
+        _check(lib().kaiju_gpu_tally_pass_ms(self._h, ms.ctypes.data, TALLY_PASSES))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_tally_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def table_text(names: TaxonNames, entries, totals, label, rank, ranks=None, min_percent=0.0, min_count=0, expand_viruses=False,
+               filter_unclassified=False, full_path=False) -> bytes:
+    """the rows kaiju2table prints for one input file (kaiju_table_rows; host only): ``entries`` and ``totals`` as
+    Tally.result gives them, ``label`` for the file column; the other arguments are the tool's -r, -l, -m, -c, -e, -u, -p.
+    Options the tool refuses raise KaijuGpuError.  No header row."""
+    entries = np.ascontiguousarray(entries, dtype=TALLY_ENTRY_DTYPE)
+    totals = np.array([totals], dtype=TALLY_INFO_DTYPE)
+    flags = (TABLE_EXPAND_VIRUSES if expand_viruses else 0) | (TABLE_FILTER_UNCLASSIFIED if filter_unclassified else 0) | (TABLE_FULL_PATH if full_path else 0)
+    opt = TableOptions(rank.encode(), ranks.encode() if ranks else None, float(min_percent), int(min_count), flags, 0)
+    label = label if isinstance(label, bytes) else label.encode()
+    n = C.c_uint64()
+    args = (names._h, entries.ctypes.data if entries.size else None, entries.size, totals.ctypes.data, C.byref(opt), label)
+    _check(lib().kaiju_table_rows(*args, None, 0, C.byref(n)))
+    buf = np.zeros(n.value + 1, dtype=np.uint8)
+    _check(lib().kaiju_table_rows(*args, buf.ctypes.data, n.value, C.byref(n)))
+    return buf[:n.value].tobytes()
 
 
 class Classifier:

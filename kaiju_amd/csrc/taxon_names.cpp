@@ -22,6 +22,7 @@
 #include "../../include/kaiju_gpu.h"
 #include "kj_format_names.h"
 #include "taxon_names.h"
+#include "host/table_rows.h"
 
 using namespace kjn;
 
@@ -136,6 +137,8 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
   N.name_len.assign(cap, kGenerated);
   N.rank.assign(cap, (uint8_t)kNoRank);
   N.n_nodes = order.size();
+  N.rank_of.assign(cap, 0);
+  std::unordered_map<std::string, uint16_t> rank_index;
   for (uint64_t id : order) {
     if (id == ~0ull) return fail(KAIJU_GPU_ERR_ARG, "taxon id 2^64 - 1 cannot be a node");
     uint32_t s = hash_id(id) & (cap - 1);
@@ -147,6 +150,12 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
     const Node &nd = nodes[id];
     N.parent[s] = find_slot(N.key.data(), cap - 1, nd.parent);
     N.name_len[s] = kGenerated | (8 + kjf::digits_u64(id));
+    const auto ri = rank_index.emplace(nd.rank, (uint16_t)N.rank_names.size());
+    if (ri.second) {
+      if (N.rank_names.size() == 0xffff) return fail(KAIJU_GPU_ERR_ARG, "more than 65535 distinct ranks");
+      N.rank_names.push_back(nd.rank);
+    }
+    N.rank_of[s] = ri.first->second;
     if (nd.rank != "no rank")
       for (size_t k = 0; k < N.ranks.size(); k++)
         if (N.ranks[k] == nd.rank) N.rank[s] = (uint8_t)k;
@@ -236,4 +245,28 @@ extern "C" int64_t kaiju_taxon_names_annotation(const kaiju_taxon_names *names, 
     if (cap && !text.empty()) memcpy(buf, text.data(), text.size() < cap ? text.size() : (size_t)cap);
     return (int64_t)text.size();
   } catch (const std::exception &) { return -1; }
+}
+
+// the rows of kaiju2table (host/table_rows.h) behind the C interface
+extern "C" int kaiju_table_rows(const kaiju_taxon_names *names, const kaiju_gpu_tally_entry *entries, uint64_t n_entries, const kaiju_gpu_tally_info *totals,
+                                const kaiju_table_options *opt, const char *label, char *buf, uint64_t cap, uint64_t *n_bytes) {
+  if (!names || (!entries && n_entries) || !totals || !opt || !opt->rank || !label || (!buf && cap) || !n_bytes) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  try {
+    kjtr::Options o;
+    o.rank = opt->rank;
+    o.has_list = opt->ranks_csv && *opt->ranks_csv;
+    if (o.has_list) o.list = kjtr::split_ranks(opt->ranks_csv);
+    o.min_percent = opt->min_percent;
+    o.min_count = opt->min_count;
+    o.expand_viruses = opt->flags & KAIJU_TABLE_EXPAND_VIRUSES;
+    o.filter_unclassified = opt->flags & KAIJU_TABLE_FILTER_UNCLASSIFIED;
+    o.full_path = opt->flags & KAIJU_TABLE_FULL_PATH;
+    if (const char *why = kjtr::refusal(o)) return fail(KAIJU_GPU_ERR_ARG, why);
+    const std::string text = kjtr::table_rows(*names, entries, n_entries, *totals, o, label);
+    *n_bytes = text.size();
+    if (cap && !text.empty()) memcpy(buf, text.data(), text.size() < cap ? text.size() : (size_t)cap);
+    return KAIJU_GPU_OK;
+  }
+  catch (const std::bad_alloc &) { return fail(KAIJU_GPU_ERR_NOMEM, "out of host memory"); }
+  catch (const std::exception &e) { return fail(KAIJU_GPU_ERR_ARG, std::string("unexpected error: ") + e.what()); }
 }

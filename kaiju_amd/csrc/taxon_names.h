@@ -23,6 +23,9 @@ struct kaiju_taxon_names {
   std::vector<std::string> ranks;     // the de-duplicated list
   std::vector<uint8_t> list;          // the list as given: per item the index in `ranks`
   uint64_t n_nodes = 0, n_named = 0;
+  // in every mode, for the rows of kaiju2table (host/table_rows.h): the rank of every node as nodes.dmp spells it
+  std::vector<std::string> rank_names; // the distinct rank strings, "no rank" among them
+  std::vector<uint16_t> rank_of;       // [cap] index in rank_names (empty slots: 0)
 };
 
 // what a failed call of taxon_names.cpp said (it is also given to kaiju_gpu_last_error() where capi.hip is linked)
