@@ -700,6 +700,47 @@ int kaiju_gpu_tally_result(kaiju_gpu_tally *t, kaiju_gpu_tally_entry *entries, u
 enum { KAIJU_GPU_TALLY_PASSES = 3 };
 int kaiju_gpu_tally_pass_ms(kaiju_gpu_tally *t, float *ms, uint32_t n);
 
+/* ---- kaiju2krona on the counts of tallies: one lineage line per taxon -------------------------------------------- */
+/* What kaiju2krona.cpp:150-190 writes from its counts, written on the device from the direct counts that tallies hold there
+   (kaiju_amd/csrc/krona.hip; the rules: kj_krona.h): for every node with reads and a name of its own the line
+   "<reads>\t<name>\t<name>...\n", the lineage root first.  The taxon's own name is printed when its parent's id has a name; an
+   ancestor without a name is left out; a parent id that is no node but has a name in names.dmp is printed in front (without a
+   list of ranks only).  ranks_csv (the tool's -l; NULL: none): items between commas, empty ones dropped; only names of nodes
+   whose rank string is an item are printed, "no rank" being a rank like any other.  The lines are in ascending slot order -
+   that of kaiju_gpu_tally_result; the tool's order is that of a hash map - and "<n>\tUnclassified\n" is the last one.
+   `names` may be of any mode and must outlive the object; its lineage tables (1 + 1 + 4 bytes per slot, and the names of
+   parent ids that are no nodes) are built at create.  KAIJU_GPU_ERR_ARG for a list of more than KAIJU_NAMES_MAX_LIST items
+   and for a lineage of 2^24 bytes or more. */
+typedef struct kaiju_gpu_krona kaiju_gpu_krona;
+enum { KAIJU_GPU_KRONA_MAX_TALLIES = 4 };
+int kaiju_gpu_krona_create(const kaiju_gpu_taxon_names *names, const char *ranks_csv, kaiju_gpu_krona **out);
+void kaiju_gpu_krona_free(kaiju_gpu_krona *k);
+typedef struct kaiju_gpu_krona_info {
+  uint64_t text_bytes;             /* of the whole text, also when it overflowed: a call with out_cap == 0 sizes the buffer  */
+  uint64_t written_bytes;          /* of the lines that were written                                                       */
+  uint64_t n_lines, n_written;     /* lines of the whole text / written                                                    */
+  uint64_t n_unnamed_taxa;         /* nodes with reads and no name of their own: no line ...                               */
+  uint64_t n_unnamed_reads;        /* ... and their reads                                                                  */
+  uint64_t n_unclassified;         /* the count of the Unclassified line (0: no such line)                                 */
+  uint32_t overflow, reserved;     /* 1: the text is longer than out_cap; only whole lines in front of out_cap were written */
+} kaiju_gpu_krona_info;            /* 64 bytes */
+/* The text of the counts of tallies[0 .. n_tallies) (1 .. KAIJU_GPU_KRONA_MAX_TALLIES of them, all on the names of `k`; their
+   counts are added per slot and stay as they are).  count_unclassified != 0 (the tool's -u): the Unclassified line, if any
+   line was unclassified.  All pointers device pointers; the call waits on the events of the tallies, every pass is queued on
+   `stream` (NULL: a stream of the object) and nothing synchronises.  d_out is 16-byte aligned.  A line is written whole or
+   not at all and no byte at or behind out_cap is touched.  One call at a time per object.  KAIJU_GPU_ERR_ARG for a tally of
+   other names or another device, for 0 or too many tallies and for a misaligned d_out. */
+int kaiju_gpu_krona_text_device(kaiju_gpu_krona *k, kaiju_gpu_tally *const *tallies, uint32_t n_tallies, int count_unclassified, void *d_out,
+                                uint64_t out_cap, kaiju_gpu_krona_info *d_info, void *stream);
+/* The same into host memory; blocks.  cap == 0 with buf == NULL: only the info */
+int kaiju_gpu_krona_text(kaiju_gpu_krona *k, kaiju_gpu_tally *const *tallies, uint32_t n_tallies, int count_unclassified, char *buf, uint64_t cap,
+                         kaiju_gpu_krona_info *info);
+/* Diagnostics.  An object created with KAIJU_GPU_KRONA_TIMES=1 in the environment records a HIP event between the passes of
+   every call (KAIJU_GPU_ERR_UNSUPPORTED otherwise): the milliseconds of the last call's passes - select, compact, len and
+   offsets, write, finish - into ms[0 .. n), n <= KAIJU_GPU_KRONA_PASSES.  Waits for that call. */
+enum { KAIJU_GPU_KRONA_PASSES = 5 };
+int kaiju_gpu_krona_pass_ms(kaiju_gpu_krona *k, float *ms, uint32_t n);
+
 /* ---- the rows of kaiju2table (host only, no GPU) -------------------------------------------------------------- */
 enum { KAIJU_TABLE_EXPAND_VIRUSES = 1, KAIJU_TABLE_FILTER_UNCLASSIFIED = 2, KAIJU_TABLE_FULL_PATH = 4 };   /* -e, -u, -p */
 typedef struct kaiju_table_options {

@@ -96,6 +96,10 @@ TALLY_INFO_DTYPE = np.dtype([("used", "<u8"), ("n_lines", "<u8"), ("n_total", "<
 TALLY_ENTRY_DTYPE = np.dtype([("taxon", "<u8"), ("direct", "<u8"), ("summed", "<u8"), ("virus", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_tally_entry
 assert TALLY_INFO_DTYPE.itemsize == 56 and TALLY_ENTRY_DTYPE.itemsize == 32
 TALLY_PASSES = 3
+KRONA_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("written_bytes", "<u8"), ("n_lines", "<u8"), ("n_written", "<u8"), ("n_unnamed_taxa", "<u8"),
+                             ("n_unnamed_reads", "<u8"), ("n_unclassified", "<u8"), ("overflow", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_krona_info
+assert KRONA_INFO_DTYPE.itemsize == 64
+KRONA_MAX_TALLIES, KRONA_PASSES = 4, 5
 TABLE_EXPAND_VIRUSES, TABLE_FILTER_UNCLASSIFIED, TABLE_FULL_PATH = 1, 2, 4
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
@@ -245,6 +249,12 @@ def lib():
         L.kaiju_gpu_tally_add_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
         L.kaiju_gpu_tally_result.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.kaiju_gpu_tally_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "kaiju_gpu_krona_create"):                  # (likewise)
+        L.kaiju_gpu_krona_create.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+        L.kaiju_gpu_krona_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_krona_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_krona_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_krona_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     if hasattr(L, "kaiju_table_rows"):
         L.kaiju_table_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TableOptions), C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -686,6 +696,70 @@ class Tally:
     def close(self):
         if self._h:
             lib().kaiju_gpu_tally_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Krona:
+    """kaiju2krona's text from the counts of tallies on the device of ``dnames`` (kaiju_gpu_krona_create): one line per taxon
+    with reads, "<reads>\t<name>\t<name>...\n" with the lineage root first.  ranks: the text of the tool's -l (None: no
+    list).  ``dnames`` may be of any mode."""
+
+    def __init__(self, dnames: DeviceTaxonNames, ranks=None):
+        if not hasattr(lib(), "kaiju_gpu_krona_create"):
+            raise KaijuGpuError("this library was linked without krona.hip")
+        self._names = dnames                                  # (the tables must outlive the object)
+        self._h = C.c_void_p()
+        if ranks is not None and not isinstance(ranks, bytes):
+            ranks = ranks.encode()
+        _check(lib().kaiju_gpu_krona_create(dnames._h, ranks, C.byref(self._h)))
+
+    @staticmethod
+    def _handles(tallies):
+        tallies = [tallies] if isinstance(tallies, Tally) else list(tallies)
+        return (C.c_void_p * max(len(tallies), 1))(*[t._h for t in tallies]), len(tallies)
+
+    def text(self, tallies, unclassified=False, out_cap=None, out=None):
+        """Returns (bytes, info): the lines of the counts of ``tallies`` (a Tally or up to KRONA_MAX_TALLIES of them, added per
+        taxon) and a KRONA_INFO_DTYPE record.  unclassified: the tool's -u.  out_cap: the capacity (default: the size of the
+        text, found by a call with none); when the text overflows it, info["overflow"] is set and only whole lines in front of
+        it are written.  out: a uint8 array of at least out_cap bytes to write into; the first value returned is then None"""
+        h, n = self._handles(tallies)
+        info = np.zeros(1, dtype=KRONA_INFO_DTYPE)
+        if out_cap is None:
+            _check(lib().kaiju_gpu_krona_text(self._h, h, n, 1 if unclassified else 0, None, 0, info.ctypes.data))
+            out_cap = int(info[0]["text_bytes"])
+        cap = int(out_cap)
+        own = out is None
+        if own:
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.size >= cap
+        _check(lib().kaiju_gpu_krona_text(self._h, h, n, 1 if unclassified else 0, out.ctypes.data if cap else None, cap, info.ctypes.data))
+        if not own:
+            return None, info[0]
+        return bytes(out[:int(info[0]["written_bytes"])]), info[0]
+
+    def text_device(self, tallies, d_out_ptr: int, out_cap: int, d_info_ptr: int, unclassified=False, stream: int = 0):
+        """the same into device memory (raw pointers, d_out 16-byte aligned): kaiju_gpu_krona_text_device, asynchronous on
+        ``stream`` behind the calls of the tallies"""
+        h, n = self._handles(tallies)
+        _check(lib().kaiju_gpu_krona_text_device(self._h, h, n, 1 if unclassified else 0, d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def pass_ms(self):
+        """milliseconds of the last call's passes (select, compact, len and offsets, write, finish); needs
+        KAIJU_GPU_KRONA_TIMES=1 at creation"""
+        ms = np.zeros(KRONA_PASSES, dtype=np.float32)
+        _check(lib().kaiju_gpu_krona_pass_ms(self._h, ms.ctypes.data, KRONA_PASSES))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_krona_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -31,6 +31,7 @@ struct kaiju_gpu_taxon_names {
   Tab tab{};
   uint32_t cap = 0;
   uint64_t max_annotation = 0;
+  kaiju_krona_source krona;            // host side, for krona.hip
   std::vector<void *> allocs;
   ~kaiju_gpu_taxon_names() {
     if (device < 0) return;
@@ -202,6 +203,7 @@ extern "C" int kaiju_gpu_taxon_names_upload(const kaiju_taxon_names *names, int 
       return fail(KAIJU_GPU_ERR_HIP, "the kernel that builds the name tables");
     T.path_len = path_len; T.rank_src = rank_src; T.rank_len = rank_len;
     g->max_annotation = most;
+    g->krona = kaiju_krona_source{names->rank_names, names->rank_of, names->dang_pos, names->dang_len, names->dang_blob};
     if (most >= kMaxAnnotation) return fail(KAIJU_GPU_ERR_ARG, "an annotation of " + std::to_string(most) + " bytes: 2^24 or more");
     *out = g.release();
     return KAIJU_GPU_OK;
@@ -212,6 +214,7 @@ extern "C" void kaiju_gpu_taxon_names_free(kaiju_gpu_taxon_names *names) { delet
 extern "C" uint64_t kaiju_gpu_taxon_names_max_annotation(const kaiju_gpu_taxon_names *names) { return names ? names->max_annotation : 0; }
 int kj_fn_device(const kaiju_gpu_taxon_names *names) { return names ? names->device : -1; }
 const kjn::Tab *kj_fn_tab(const kaiju_gpu_taxon_names *names) { return names ? &names->tab : nullptr; }   // (for annotate.hip)
+const kaiju_krona_source *kj_fn_krona_source(const kaiju_gpu_taxon_names *names) { return names ? &names->krona : nullptr; }   // (for krona.hip)
 
 extern "C" int kaiju_gpu_taxon_names_read(const kaiju_gpu_taxon_names *names, int which, void *host_out, uint64_t out_bytes, uint64_t *n_slots) {
   if (!names || (!host_out && out_bytes)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");

@@ -35,6 +35,7 @@
 
 #include "capi_internal.h"
 #include "kj_tally.h"
+#include "kj_krona.h"
 #include "kj_lines.h"
 
 using namespace kjt;
@@ -399,6 +400,9 @@ extern "C" void kaiju_gpu_tally_free(kaiju_gpu_tally *a) {
   }
   delete a;
 }
+
+// for krona.hip, which reads the counts where they lie
+kj_tally_view kj_tally_view_of(const kaiju_gpu_tally *a) { return kj_tally_view{a->names, a->device, a->direct, a->totals, a->done}; }
 
 extern "C" int kaiju_gpu_tally_reset(kaiju_gpu_tally *a) {
   return guarded([&]() -> int {

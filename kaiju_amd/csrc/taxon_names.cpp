@@ -138,6 +138,9 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
   N.rank.assign(cap, (uint8_t)kNoRank);
   N.n_nodes = order.size();
   N.rank_of.assign(cap, 0);
+  N.dang_pos.assign(cap, 0);
+  N.dang_len.assign(cap, 0);
+  std::unordered_map<uint64_t, std::vector<uint32_t>> orphans;    // a parent id that is no node -> the slots below it
   std::unordered_map<std::string, uint16_t> rank_index;
   for (uint64_t id : order) {
     if (id == ~0ull) return fail(KAIJU_GPU_ERR_ARG, "taxon id 2^64 - 1 cannot be a node");
@@ -149,6 +152,7 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
     const uint32_t s = find_slot(N.key.data(), cap - 1, id);
     const Node &nd = nodes[id];
     N.parent[s] = find_slot(N.key.data(), cap - 1, nd.parent);
+    if (N.parent[s] == kNone) orphans[nd.parent].push_back(s);
     N.name_len[s] = kGenerated | (8 + kjf::digits_u64(id));
     const auto ri = rank_index.emplace(nd.rank, (uint16_t)N.rank_names.size());
     if (ri.second) {
@@ -195,7 +199,18 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
     s = q++;
     while (q < e && *q != '\t' && *q != '|') q++;
     const uint32_t slot = find_slot(N.key.data(), cap - 1, id);
-    if (slot == kNone || !(N.name_len[slot] & kGenerated)) return;          // no node (never looked up), or it has its name
+    if (slot == kNone) {                                                      // no node: kaiju2krona prints it above its orphans
+      const auto o = orphans.find(id);
+      if (o == orphans.end() || N.dang_len[o->second[0]]) return;
+      if ((uint64_t)(q - s) >= kMaxAnnotation || N.dang_blob.size() + (size_t)(q - s) > 0xfffffff0ull) {   // (kaiju_gpu_krona_create refuses it)
+        for (uint32_t below : o->second) N.dang_len[below] = kNone;
+        return;
+      }
+      for (uint32_t below : o->second) { N.dang_pos[below] = (uint32_t)N.dang_blob.size(); N.dang_len[below] = (uint32_t)(q - s); }
+      N.dang_blob.insert(N.dang_blob.end(), s, q);
+      return;
+    }
+    if (!(N.name_len[slot] & kGenerated)) return;                             // it has its name
     if ((uint64_t)(q - s) >= kMaxAnnotation || N.blob.size() + (size_t)(q - s) > 0xfffffff0ull) { too_long = true; return; }
     N.name_pos[slot] = (uint32_t)N.blob.size();
     N.name_len[slot] = (uint32_t)(q - s);
@@ -204,6 +219,7 @@ static int load(const char *nodes_dmp, const char *names_dmp, int mode, const ch
   });
   if (too_long) return fail(KAIJU_GPU_ERR_ARG, "a name of 2^24 bytes or more, or 4 GiB of names");
   N.blob.resize(N.blob.size() + 16, 0);               // (never read: room for an aligned load at the end)
+  N.dang_blob.resize(N.dang_blob.size() + 16, 0);
   guard.p = nullptr;
   *out = raw;
   return KAIJU_GPU_OK;

@@ -26,6 +26,20 @@ struct kaiju_taxon_names {
   // in every mode, for the rows of kaiju2table (host/table_rows.h): the rank of every node as nodes.dmp spells it
   std::vector<std::string> rank_names; // the distinct rank strings, "no rank" among them
   std::vector<uint16_t> rank_of;       // [cap] index in rank_names (empty slots: 0)
+  // in every mode, for the lineage lines of kaiju2krona (kj_krona.h): the name of a parent id that is no node.  One per
+  // orphan at most, in a blob of their own: no table above changes by them
+  std::vector<uint32_t> dang_pos;      // [cap] where the name of the slot's parent id starts in dang_blob
+  std::vector<uint32_t> dang_len;      // [cap] its bytes; 0: the parent is a node, or its id has no name; kjn::kNone: a name of 2^24 bytes or more
+  std::vector<uint8_t> dang_blob;
+};
+
+// what kaiju2krona needs beyond the slot tables on the device: kaiju_gpu_taxon_names_upload keeps a copy on the host, and
+// kaiju_gpu_krona_create (krona.hip) makes its tables from it
+struct kaiju_krona_source {
+  std::vector<std::string> rank_names;
+  std::vector<uint16_t> rank_of;
+  std::vector<uint32_t> dang_pos, dang_len;
+  std::vector<uint8_t> dang_blob;
 };
 
 // what a failed call of taxon_names.cpp said (it is also given to kaiju_gpu_last_error() where capi.hip is linked)
