@@ -33,7 +33,7 @@ def needs_build():
 
 
 MKFMI_LIB = os.path.join(HERE, "libkaiju_mkfmi.so")
-MKFMI_SRC = [os.path.join(CSRC, "mkfmi.cpp"), os.path.join(CSRC, "mkfmi.h")]
+MKFMI_SRC = [os.path.join(CSRC, "mkfmi.cpp"), os.path.join(CSRC, "mkfmi.h"), os.path.join(CSRC, "kj_fmibuild.h")]
 
 
 def build_mkfmi(force=False, verbose=False):
@@ -47,15 +47,16 @@ def build_mkfmi(force=False, verbose=False):
 
 
 MKFMI_GPU_LIB = os.path.join(HERE, "libkaiju_mkfmi_gpu.so")
-MKFMI_GPU_SRC = [os.path.join(CSRC, f) for f in ("mkfmi.cpp", "sufsort.hip", "mkfmi.h", "kj_sufsort.h")]
+MKFMI_GPU_SRC = [os.path.join(CSRC, f) for f in ("mkfmi.cpp", "sufsort.hip", "fmibuild.hip", "mkfmi.h", "kj_sufsort.h", "kj_fmibuild.h")]
 
 
 def build_mkfmi_gpu(force=False, verbose=False):
-    """the index builder with the suffix sort on the device (csrc/kj_sufsort.h): the host builder's source with a define plus
-    sufsort.hip, a third library - libkaiju_mkfmi.so stays free of HIP and libkaiju_gpu.so free of the builder"""
+    """the index builder with the suffix sort (csrc/kj_sufsort.h) and, asked to, the stages behind it (csrc/kj_fmibuild.h) on the
+    device: the host builder's source with a define plus sufsort.hip and fmibuild.hip, a third library - libkaiju_mkfmi.so stays
+    free of HIP and libkaiju_gpu.so free of the builder"""
     if force or not os.path.exists(MKFMI_GPU_LIB) or any(os.path.getmtime(d) > os.path.getmtime(MKFMI_GPU_LIB) for d in MKFMI_GPU_SRC):
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc", "-Wno-unused-result",
-               "-DKAIJU_MKFMI_GPU", "-o", MKFMI_GPU_LIB] + MKFMI_GPU_SRC[:2] + ["-lpthread"]
+               "-DKAIJU_MKFMI_GPU", "-o", MKFMI_GPU_LIB] + MKFMI_GPU_SRC[:3] + ["-lpthread"]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)

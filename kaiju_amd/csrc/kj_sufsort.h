@@ -134,6 +134,14 @@ struct kaiju_sufsort_stats;
 int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
                       std::string &err);
 int kj_sufsort_check_device(int device_id, std::string &err);
+// the same sort for the stages that follow it on the device (kj_fmibuild.h): what stays in device memory when it ends
+struct SsKeep {
+  void *text = nullptr, *rank = nullptr, *sa = nullptr, *k0 = nullptr, *temp = nullptr;   // ss_text_alloc(tlen) bytes, 4 x tlen rounded up to 16, 4 nsuf, 8 nsuf, temp_bytes
+  uint64_t temp_bytes = 0, nseq = 0, nsuf = 0, maxlen = 0, bytes = 0;                     // bytes: what the sort had allocated
+};
+int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                           SsKeep *keep, std::string &err);
+uint64_t kj_sufsort_need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t *temp_bytes_out);
 #endif
 
 #endif

@@ -20,7 +20,10 @@
 // Suffixes are sorted bucket-wise (first three symbols) with std::sort on a word-at-a-time
 // comparator, buckets in parallel (sort_suffixes_host) - or, compiled with -DKAIJU_MKFMI_GPU into
 // libkaiju_mkfmi_gpu.so and asked to, on a GPU (sort_suffixes_device: kj_sufsort.h, sufsort.hip).
-// Everything behind the sorted suffix array is the same host code either way.
+// Everything behind the sorted suffix array - BWT of the file, sequence ranks, replication, samples, checkpoints, byte coding -
+// fills one struct of arrays (FmiArrays) from which the file is written: stages_host, the loops below, or, in
+// libkaiju_mkfmi_gpu.so and asked to, stages_device (kj_fmibuild.h, fmibuild.hip), which sorts on the GPU as well and leaves
+// the suffix array there.  Header, names and the write are one copy.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -38,6 +41,7 @@
 #include <vector>
 
 #include "mkfmi.h"
+#include "kj_fmibuild.h"
 #ifdef KAIJU_MKFMI_GPU
 #include "kj_sufsort.h"
 #endif
@@ -61,8 +65,6 @@ struct BuildClock {
 };
 
 struct Seq { std::string id; uint64_t start; uint64_t len; };
-
-int bits_needed(long k) { int i = 0; while (k >> i) ++i; return i; }   // suffixArray.c:57
 
 template <class F> void parallel_chunks(unsigned nt, uint64_t n, F &&fn) {
   if (nt <= 1 || n < 2) { fn(0, n, 0u); return; }
@@ -311,7 +313,8 @@ int sort_suffixes_host(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, u
 #ifdef KAIJU_MKFMI_GPU
 // on the device (sufsort.hip): 32-bit positions, widened here for the 64-bit instantiation
 template <class I>
-int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, int device_id, RawArr<I> &SA, BuildClock &bc) {
+int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, int device_id, RawArr<I> &SA, BuildClock &bc,
+                         kaiju_sufsort_stats *stats_out = nullptr) {
   uint64_t n = 0;
   int rc;
   kaiju_sufsort_stats st;
@@ -324,6 +327,7 @@ int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf,
   }
   if (rc != KAIJU_GPU_OK) return rc;
   if (n != nsuf) { g_err = "internal: suffix count"; return KAIJU_GPU_ERR_ARG; }
+  if (stats_out) *stats_out = st;
   bc.mark("suffix sort");
   if (bc.on) {                                   // what the mark is made of: upload + rounds + download by HIP events, active suffixes per round
     fprintf(stderr, "[kaiju mkfmi]   on device %d: %.1f ms, %u rounds, active", device_id, st.ms_sort, st.rounds);
@@ -334,167 +338,32 @@ int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf,
 }
 #endif
 
-// copies > 1: the index of the database in which every sequence of the FASTA file occurs `copies` times in a row (copy t of
-// sequence i is sequence i * copies + t of that database) - WITHOUT sorting it again: equal suffixes of different sequences
-// compare by file order, so row r of the index of the file becomes the rows r * copies .. r * copies + copies - 1.  The output
-// is byte for byte what this builder (and the reference's) writes for the FASTA with the repeats spelled out
-// (tests/test_mkfmi_pin.py); a 2^32-row index for the tests of the wide path takes half a minute this way instead of the
-// seven minutes of sorting 4.3 G suffixes.  copy_taxids (optional): copy t of a sequence named X_<id> is named
-// X_<copy_taxids[(i + t) % n]>, so that the copies do not all carry one taxon.
-template <class I>
-int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t copies = 1, const uint64_t *copy_taxids = nullptr,
-          uint32_t n_copy_taxids = 0, int device_id = -1) {
-  // alphabet of kaiju-makedb:373 with the terminator in front (mkbwt.c:read_alphabet)
-  const char alphabet[] = "*ACDEFGHIKLMNPQRSTVWY";
-  const int alen = 21;
-  signed char trans[128];
-  trans[0] = 0;
-  for (int i = 1; i < 128; i++) trans[i] = isalpha(i) ? (signed char)(alen - 1) : (signed char)-1;
-  for (int i = 0; i < alen; i++) { trans[toupper(alphabet[i])] = (signed char)i; trans[tolower(alphabet[i])] = (signed char)i; }
-  // the reference's table maps the terminator character itself ('*') to code 0, i.e. a '*' inside
-  // the FASTA would plant a terminator in the middle of a sequence; it is skipped here
-  trans[(int)'*'] = -1;
-  std::vector<Seq> seqs;
-  RawArr<uint8_t> T;
-  BuildClock bc;
-  const unsigned nt = (unsigned)std::max(1, threads);
-  uint64_t tlen = 0;                              // == bwtlen of the file's own index
-  if (!read_fasta(faa, trans, nt, seqs, T, tlen)) return KAIJU_GPU_ERR_IO;
-  const uint64_t nseq = seqs.size();
-  bc.mark("read FASTA");
-  if (sizeof(I) == 4 && tlen >= 0xfffffff0ull) { g_err = "internal: index type too small"; return KAIJU_GPU_ERR_ARG; }
+// ---- the stages behind the sort: two implementations of "fill the arrays of the file" -----------------------------------------
+// what the file is written from, whoever made it
+struct FmiArrays {
+  FbPlan P;
+  std::vector<uint32_t> read_of_rank;      // [nseq]
+  RawArr<uint8_t> sa;                      // [ncheck * nbytes]
+  RawArr<uint8_t> B, bwt_own;              // BWT of the file's own index; of the output when copies > 1
+  uint8_t *bwt = nullptr;                  // [otlen]: one of the two
+  std::vector<int64_t> index1;             // [N1 * 21]
+  RawArr<uint16_t> index2;                 // [N2 * 21]
+  int startLcode[32] = {0};
+};
 
-  // ---- the suffix array of the letter suffixes (device_id >= 0: sorted on that GPU, libkaiju_mkfmi_gpu.so only) ---------------
-  const uint64_t nsuf = tlen - nseq;
-  RawArr<I> SA(nsuf);
-  {
-    int rc;
-#ifdef KAIJU_MKFMI_GPU
-    if (device_id >= 0) rc = sort_suffixes_device<I>(T, tlen, nsuf, device_id, SA, bc);
-    else
-#endif
-      rc = sort_suffixes_host<I>(T, tlen, nsuf, nt, SA, bc);
-    if (rc != KAIJU_GPU_OK) return rc;
-  }
-
-  // ---- BWT of the file's own index: rows 0 .. nseq-1 are the terminator suffixes in file order, then the sorted suffixes;
-  //      a terminator in front of a suffix says that it is a whole sequence --------------------------------------------
-  RawArr<uint8_t> B(tlen);
-  parallel_chunks(nt, tlen, [&](uint64_t b, uint64_t e, unsigned) {
-    for (uint64_t r = b; r < e; r++) {
-      if (r < nseq) B[r] = seqs[r].len ? T[seqs[r].start + seqs[r].len - 1] : 0;
-      else { const uint64_t p = SA[r - nseq]; B[r] = p ? T[p - 1] : 0; }
-    }
-  });
-  bc.mark("BWT of the file");
-  // ---- sequence ranks (order of the whole-sequence suffixes), names in sorted order ---------
-  std::vector<uint64_t> starts(nseq);
-  for (uint64_t i = 0; i < nseq; i++) starts[i] = seqs[i].start;
-  auto seq_index = [&](uint64_t p) { return (uint64_t)(std::upper_bound(starts.begin(), starts.end(), p) - starts.begin() - 1); };
-  std::vector<uint32_t> rank_of(nseq, 0), read_of_rank(nseq, 0);
-  {
-    uint32_t r0 = 0;
-    for (uint64_t i = 0; i < nseq; i++) if (seqs[i].len == 0) { rank_of[i] = r0; read_of_rank[r0] = (uint32_t)i; r0++; }   // empty sequences sort first
-    std::vector<uint64_t> zc(nt + 1, 0);
-    parallel_chunks(nt, nsuf, [&](uint64_t b, uint64_t e, unsigned t) {
-      uint64_t z = 0;
-      for (uint64_t k = b; k < e; k++) z += B[nseq + k] == 0;
-      zc[t + 1] = z;
-    });
-    for (unsigned t = 0; t < nt; t++) zc[t + 1] += zc[t];
-    if (r0 + zc[nt] != nseq) { g_err = "internal: sequence ranks"; return KAIJU_GPU_ERR_ARG; }
-    parallel_chunks(nt, nsuf, [&](uint64_t b, uint64_t e, unsigned t) {
-      uint64_t r = r0 + zc[t];
-      for (uint64_t k = b; k < e; k++) if (B[nseq + k] == 0) {
-        const uint64_t i = seq_index(SA[k]);
-        rank_of[i] = (uint32_t)r; read_of_rank[r] = (uint32_t)i; r++;
-      }
-    });
-  }
-  bc.mark("sequence ranks");
-
-  // ---- BWT -----------------------------------------------------------------------------------
-  const uint64_t N = copies < 1 ? 1 : copies;
-  const uint64_t otlen = tlen * N, onseq = nseq * N;          // what the output describes
-  if (onseq >= 0x7fffffffull) { g_err = "too many sequences for the .fmi header (int32)"; return KAIJU_GPU_ERR_ARG; }
-  RawArr<uint8_t> bwt_own;
-  uint8_t *bwt = B.data();
-  if (N > 1) {
-    bwt_own.alloc(otlen);
-    bwt = bwt_own.data();
-    parallel_chunks(nt, tlen, [&](uint64_t b, uint64_t e, unsigned) {
-      for (uint64_t r = b; r < e; r++) memset(bwt + r * N, B[r], (size_t)N);
-    });
-  }
-  bc.mark("BWT");
-
-  // ---- suffix array samples (init_suffixArray suffixArray.c:140-180) -------------------------
-  long maxlen = 0;
-  for (auto &s : seqs) if ((long)s.len > maxlen) maxlen = (long)s.len;
-  const int sbits = bits_needed((long)onseq), pbits = bits_needed(maxlen);
-  const int nbytes = (7 + sbits + pbits) / 8;
-  const int64_t ncheck = (int64_t)(otlen >> chpt_exp) - (int64_t)(onseq >> chpt_exp);   // the header value
-  const int64_t mask = (1 << pbits) - 1, check = (1 << chpt_exp) - 1;
-  RawArr<uint8_t> sa((uint64_t)std::max<int64_t>(ncheck, 0) * nbytes);
-  {
-    const uint64_t step = 1ull << chpt_exp;
-    const uint64_t first = ((onseq + step - 1) >> chpt_exp) << chpt_exp;   // first sampled row >= nseq
-    const uint64_t nsamp = first < otlen ? ((otlen - 1 - first) >> chpt_exp) + 1 : 0;
-    if ((int64_t)nsamp < ncheck) memset(sa.data() + nsamp * nbytes, 0, (size_t)(ncheck - (int64_t)nsamp) * nbytes);
-    parallel_chunks(nt, nsamp, [&](uint64_t b, uint64_t e, unsigned) {
-      for (uint64_t q = b; q < e; q++) {
-        if ((int64_t)q >= ncheck) break;            // mkfmi only carries ncheck entries over
-        const uint64_t k = first + (q << chpt_exp);
-        const uint64_t r = k / N, t = k % N;         // row of the file's own index, copy
-        const uint64_t p = SA[r - nseq];
-        const uint64_t i = seq_index(p);
-        long val = (long)((uint64_t)rank_of[i] * N + t);
-        val = (val << pbits) + (long)(p - seqs[i].start);
-        uint8_t *c = sa.data() + q * nbytes;
-        for (int n = nbytes; n-- > 0;) { c[n] = (uint8_t)val; val >>= 8; }
-      }
-    });
-  }
-  bc.mark("suffix array samples");
-
-  // ---- FMI (fmicommon.h:77-171, compactfmi.c:108-150,399-457) ---------------------------------
-  const int64_t bwtlen = (int64_t)otlen;
-  int N1 = (int)(((bwtlen - 1) >> 16) + 2);
-  if (((int64_t)N1 << 16) == bwtlen) N1 -= 1;
-  int N2 = (int)(((bwtlen - 1) >> 8) + 2);
-  if (((int64_t)N1 << 8) == bwtlen) N2 -= 1;
-  std::vector<int64_t> index1((size_t)N1 * alen, 0);
-  RawArr<uint16_t> index2((uint64_t)N2 * alen);
+// index1 rows 0 .. npieces-1 hold the raw letter counts of the pieces, index2 the rows of the 256-row blocks that exist: the
+// running sums, the tail rows, C[] and the code table (fmicommon.h:77-171, compactfmi.c:108-150), with the quirks of the serial
+// loops of the reference
+void finish_checkpoints(const FbPlan &P, std::vector<int64_t> &index1, RawArr<uint16_t> &index2, int *startLcode) {
+  const int alen = KJ_FB_ALEN;
+  const int64_t bwtlen = (int64_t)P.otlen;
+  const int N1 = P.N1, N2 = P.N2;
   int64_t total[32] = {0};
   {
-    // letter counts of every piece of 2^16 rows, their running sums (index1 before C[] is added), then the 2^8 checkpoints
-    // of every piece relative to its start
-    const uint64_t nR1 = ((uint64_t)bwtlen + 65535) >> 16;
-    parallel_chunks(nt, nR1, [&](uint64_t b, uint64_t e, unsigned) {
-      for (uint64_t R = b; R < e; R++) {
-        int64_t h[32] = {0};
-        const uint64_t lo = R << 16, hi = std::min<uint64_t>((uint64_t)bwtlen, lo + 65536);
-        for (uint64_t ii = lo; ii < hi; ii++) h[bwt[ii]]++;
-        for (int a = 0; a < alen; a++) index1[(size_t)R * alen + a] = h[a];
-      }
-    });
+    const uint64_t nR1 = P.npieces;
     for (uint64_t R = 0; R < nR1; R++)
       for (int a = 0; a < alen; a++) { const int64_t h = index1[(size_t)R * alen + a]; index1[(size_t)R * alen + a] = total[a]; total[a] += h; }
     // (a last row of index2 behind the end of the BWT, and index1 rows behind the last piece, as the serial loop leaves them)
-    parallel_chunks(nt, nR1, [&](uint64_t b, uint64_t e, unsigned) {
-      for (uint64_t R = b; R < e; R++) {
-        int64_t run[32] = {0};
-        const uint64_t lo = R << 16, hi = std::min<uint64_t>((uint64_t)bwtlen, lo + 65536);
-        for (uint64_t ii = lo; ii < hi; ++ii) {
-          if (!(ii & 255)) {
-            const uint64_t R2 = ii >> 8;
-            if (ii > 0) for (int a = 0; a < alen; a++) index2[R2 * alen + a] = (uint16_t)run[a];
-            else for (int a = 0; a < alen; a++) index2[a] = 0;
-          }
-          run[bwt[ii]]++;
-        }
-      }
-    });
     const uint64_t R1 = ((uint64_t)bwtlen - 1) >> 16;        // the piece the serial loop was in when it ended
     const int64_t R2 = N2 - 1;
     for (uint64_t q = (((uint64_t)bwtlen - 1) >> 8) + 1; q < (uint64_t)R2; q++) for (int a = 0; a < alen; a++) index2[q * alen + a] = 0;
@@ -504,9 +373,7 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
     for (int a = 1; a < alen; a++) last[a] = last[a - 1] + total[a - 1];
     for (int64_t r = 0; r < N1 - 1; ++r) for (int a = 1; a < alen; a++) index1[(size_t)r * alen + a] += last[a];
   }
-  bc.mark("FMI checkpoints");
   // find_startLcode, compactfmi.c:108-150
-  int startLcode[32] = {0};
   {
     int maxN[32] = {0};
     int64_t tot = 0;
@@ -532,9 +399,130 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
     for (int a = 0; a < alen; a++) startLcode[a + 1] = startLcode[a] + maxN[a];
     startLcode[alen] = 256;
   }
+}
+
+// on the host: the loops over the sorted suffix array
+template <class I>
+int stages_host(const uint8_t *T, const std::vector<uint64_t> &starts, const std::vector<uint64_t> &lens, const RawArr<I> &SA, unsigned nt, int recode,
+                BuildClock &bc, FmiArrays &A) {
+  const FbPlan &P = A.P;
+  const int alen = KJ_FB_ALEN;
+  const uint64_t tlen = P.tlen, nseq = P.nseq, nsuf = P.nsuf;
+  // ---- BWT of the file's own index: rows 0 .. nseq-1 are the terminator suffixes in file order, then the sorted suffixes;
+  //      a terminator in front of a suffix says that it is a whole sequence --------------------------------------------
+  RawArr<uint8_t> &B = A.B;
+  B.alloc(tlen);
+  parallel_chunks(nt, tlen, [&](uint64_t b, uint64_t e, unsigned) {
+    for (uint64_t r = b; r < e; r++) {
+      if (r < nseq) B[r] = lens[r] ? T[starts[r] + lens[r] - 1] : 0;
+      else { const uint64_t p = SA[r - nseq]; B[r] = p ? T[p - 1] : 0; }
+    }
+  });
+  bc.mark("BWT of the file");
+  // ---- sequence ranks (order of the whole-sequence suffixes), names in sorted order ---------
+  auto seq_index = [&](uint64_t p) { return (uint64_t)(std::upper_bound(starts.begin(), starts.end(), p) - starts.begin() - 1); };
+  std::vector<uint32_t> rank_of(nseq, 0);
+  std::vector<uint32_t> &read_of_rank = A.read_of_rank;
+  read_of_rank.assign(nseq, 0);
+  {
+    uint32_t r0 = 0;
+    for (uint64_t i = 0; i < nseq; i++) if (lens[i] == 0) { rank_of[i] = r0; read_of_rank[r0] = (uint32_t)i; r0++; }   // empty sequences sort first
+    std::vector<uint64_t> zc(nt + 1, 0);
+    parallel_chunks(nt, nsuf, [&](uint64_t b, uint64_t e, unsigned t) {
+      uint64_t z = 0;
+      for (uint64_t k = b; k < e; k++) z += B[nseq + k] == 0;
+      zc[t + 1] = z;
+    });
+    for (unsigned t = 0; t < nt; t++) zc[t + 1] += zc[t];
+    if (r0 + zc[nt] != nseq) { g_err = "internal: sequence ranks"; return KAIJU_GPU_ERR_ARG; }
+    parallel_chunks(nt, nsuf, [&](uint64_t b, uint64_t e, unsigned t) {
+      uint64_t r = r0 + zc[t];
+      for (uint64_t k = b; k < e; k++) if (B[nseq + k] == 0) {
+        const uint64_t i = seq_index(SA[k]);
+        rank_of[i] = (uint32_t)r; read_of_rank[r] = (uint32_t)i; r++;
+      }
+    });
+  }
+  bc.mark("sequence ranks");
+
+  // ---- BWT -----------------------------------------------------------------------------------
+  const uint64_t N = P.copies;
+  const uint64_t otlen = P.otlen;                              // what the output describes
+  uint8_t *bwt = B.data();
+  if (N > 1) {
+    A.bwt_own.alloc(otlen);
+    bwt = A.bwt_own.data();
+    parallel_chunks(nt, tlen, [&](uint64_t b, uint64_t e, unsigned) {
+      for (uint64_t r = b; r < e; r++) memset(bwt + r * N, B[r], (size_t)N);
+    });
+  }
+  A.bwt = bwt;
+  bc.mark("BWT");
+
+  // ---- suffix array samples (init_suffixArray suffixArray.c:140-180) -------------------------
+  const int pbits = P.pbits, nbytes = P.nbytes, chpt_exp = P.chpt_exp;
+  const int64_t ncheck = P.ncheck;                              // the header value
+  RawArr<uint8_t> &sa = A.sa;
+  sa.alloc((uint64_t)std::max<int64_t>(ncheck, 0) * nbytes);
+  {
+    const uint64_t first = P.first;                             // first sampled row >= nseq
+    const uint64_t nsamp = P.nsamp;
+    if ((int64_t)nsamp < ncheck) memset(sa.data() + nsamp * nbytes, 0, (size_t)(ncheck - (int64_t)nsamp) * nbytes);
+    parallel_chunks(nt, nsamp, [&](uint64_t b, uint64_t e, unsigned) {
+      for (uint64_t q = b; q < e; q++) {
+        if ((int64_t)q >= ncheck) break;            // mkfmi only carries ncheck entries over
+        const uint64_t k = first + (q << chpt_exp);
+        const uint64_t r = k / N, t = k % N;         // row of the file's own index, copy
+        const uint64_t p = SA[r - nseq];
+        const uint64_t i = seq_index(p);
+        long val = (long)((uint64_t)rank_of[i] * N + t);
+        val = (val << pbits) + (long)(p - starts[i]);
+        uint8_t *c = sa.data() + q * nbytes;
+        for (int n = nbytes; n-- > 0;) { c[n] = (uint8_t)val; val >>= 8; }
+      }
+    });
+  }
+  bc.mark("suffix array samples");
+
+  // ---- FMI (fmicommon.h:77-171, compactfmi.c:108-150,399-457) ---------------------------------
+  const int64_t bwtlen = (int64_t)otlen;
+  std::vector<int64_t> &index1 = A.index1;
+  RawArr<uint16_t> &index2 = A.index2;
+  index1.assign((size_t)P.N1 * alen, 0);
+  index2.alloc((uint64_t)P.N2 * alen);
+  {
+    // letter counts of every piece of 2^16 rows (their running sums: finish_checkpoints), then the 2^8 checkpoints of every
+    // piece relative to its start
+    const uint64_t nR1 = ((uint64_t)bwtlen + 65535) >> 16;
+    parallel_chunks(nt, nR1, [&](uint64_t b, uint64_t e, unsigned) {
+      for (uint64_t R = b; R < e; R++) {
+        int64_t h[32] = {0};
+        const uint64_t lo = R << 16, hi = std::min<uint64_t>((uint64_t)bwtlen, lo + 65536);
+        for (uint64_t ii = lo; ii < hi; ii++) h[bwt[ii]]++;
+        for (int a = 0; a < alen; a++) index1[(size_t)R * alen + a] = h[a];
+      }
+    });
+    parallel_chunks(nt, nR1, [&](uint64_t b, uint64_t e, unsigned) {
+      for (uint64_t R = b; R < e; R++) {
+        int64_t run[32] = {0};
+        const uint64_t lo = R << 16, hi = std::min<uint64_t>((uint64_t)bwtlen, lo + 65536);
+        for (uint64_t ii = lo; ii < hi; ++ii) {
+          if (!(ii & 255)) {
+            const uint64_t R2 = ii >> 8;
+            if (ii > 0) for (int a = 0; a < alen; a++) index2[R2 * alen + a] = (uint16_t)run[a];
+            else for (int a = 0; a < alen; a++) index2[a] = 0;
+          }
+          run[bwt[ii]]++;
+        }
+      }
+    });
+    finish_checkpoints(P, index1, index2, A.startLcode);
+  }
+  bc.mark("FMI checkpoints");
   // FMIrecode, compactfmi.c:399-440: first half of a 256-block stores the number of equal letters
   // before the position, second half the number after it, saturating at the letter's top code
-  {
+  if (recode) {
+    const int *startLcode = A.startLcode;
     auto encode = [&](uint8_t c, int n) {
       const int mx = startLcode[c + 1] - startLcode[c] - 1;
       if (n > mx) n = mx;
@@ -554,8 +542,127 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
       }
     });
   }
-
   bc.mark("recode");
+  return KAIJU_GPU_OK;
+}
+
+#ifdef KAIJU_MKFMI_GPU
+// on the device (kj_fmibuild.h, fmibuild.hip): the sort and the five passes; SA never comes down.  Positions on the device are
+// 32-bit, so both instantiations of the builder take these arrays as they are.
+int stages_device(const uint8_t *T, const std::vector<uint64_t> &lens, int device_id, int recode, BuildClock &bc, FmiArrays &A,
+                  kaiju_fmi_build_stats *stats) {
+  const FbPlan &P = A.P;
+  const int alen = KJ_FB_ALEN;
+  kaiju_fmi_build_stats local;
+  if (!stats) stats = &local;
+  // (every size below is bounded by what the device can hold: the driver compares first, and allocates nothing here otherwise)
+  uint64_t r0 = 0;
+  for (uint64_t i = 0; i < P.nseq; i++) r0 += lens[i] == 0;
+  bool allocated = false;
+  std::vector<uint32_t> piece_counts;
+  const int rc = kj_fmibuild_device(
+      T, P, r0, device_id, recode,
+      [&](FbHostOut &o) {                                     // the size check has passed: room on the host for what comes down
+        A.read_of_rank.assign(P.nseq, 0);
+        uint32_t r = 0;
+        for (uint64_t i = 0; i < P.nseq; i++) if (lens[i] == 0) A.read_of_rank[r++] = (uint32_t)i;   // empty sequences sort first
+        A.sa.alloc(fb_samples_bytes(P));
+        A.B.alloc(P.otlen);
+        A.bwt = A.B.data();
+        A.index1.assign((size_t)P.N1 * alen, 0);
+        A.index2.alloc((uint64_t)P.N2 * alen);
+        piece_counts.assign((size_t)P.npieces * alen, 0);
+        o.read_of_rank = A.read_of_rank.data(); o.samples = A.sa.data(); o.bwt = A.bwt; o.piece_counts = piece_counts.data(); o.index2 = A.index2.data();
+        allocated = true;
+      },
+      [&](const uint32_t *pc, int *startLcode) {              // index2's rows and the piece counts are down: sums, tails, C[], code table
+        for (size_t k = 0; k < (size_t)P.npieces * alen; k++) A.index1[k] = pc[k];
+        finish_checkpoints(P, A.index1, A.index2, A.startLcode);
+        for (int a = 0; a <= alen; a++) startLcode[a] = A.startLcode[a];
+      },
+      [&](const char *what) { bc.mark(what); }, stats, g_err);
+  if (rc != KAIJU_GPU_OK) return rc;
+  if (!allocated) { g_err = "internal: device stages"; return KAIJU_GPU_ERR_ARG; }
+  bc.mark("device stages + download");
+  if (bc.on) {
+    fprintf(stderr, "[kaiju mkfmi]   on device %d: sort %.1f ms, %u rounds; BWT %.2f, ranks %.2f, replication + samples %.2f, checkpoints %.2f, recode %.2f, download %.2f ms; %.1f MiB\n",
+            device_id, stats->sort.ms_sort, stats->sort.rounds, stats->ms_bwt, stats->ms_ranks, stats->ms_samples, stats->ms_checkpoints, stats->ms_recode,
+            stats->ms_download, stats->device_bytes / 1048576.0);
+  }
+  return KAIJU_GPU_OK;
+}
+#endif
+
+// copies > 1: the index of the database in which every sequence of the FASTA file occurs `copies` times in a row (copy t of
+// sequence i is sequence i * copies + t of that database) - WITHOUT sorting it again: equal suffixes of different sequences
+// compare by file order, so row r of the index of the file becomes the rows r * copies .. r * copies + copies - 1.  The output
+// is byte for byte what this builder (and the reference's) writes for the FASTA with the repeats spelled out
+// (tests/test_mkfmi_pin.py); a 2^32-row index for the tests of the wide path takes half a minute this way instead of the
+// seven minutes of sorting 4.3 G suffixes.  copy_taxids (optional): copy t of a sequence named X_<id> is named
+// X_<copy_taxids[(i + t) % n]>, so that the copies do not all carry one taxon.
+template <class I>
+int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t copies = 1, const uint64_t *copy_taxids = nullptr,
+          uint32_t n_copy_taxids = 0, int device_id = -1, int stages = KAIJU_FMI_STAGES_HOST, kaiju_fmi_build_stats *stats = nullptr) {
+  // alphabet of kaiju-makedb:373 with the terminator in front (mkbwt.c:read_alphabet)
+  const char alphabet[] = "*ACDEFGHIKLMNPQRSTVWY";
+  const int alen = 21;
+  signed char trans[128];
+  trans[0] = 0;
+  for (int i = 1; i < 128; i++) trans[i] = isalpha(i) ? (signed char)(alen - 1) : (signed char)-1;
+  for (int i = 0; i < alen; i++) { trans[toupper(alphabet[i])] = (signed char)i; trans[tolower(alphabet[i])] = (signed char)i; }
+  // the reference's table maps the terminator character itself ('*') to code 0, i.e. a '*' inside
+  // the FASTA would plant a terminator in the middle of a sequence; it is skipped here
+  trans[(int)'*'] = -1;
+  std::vector<Seq> seqs;
+  RawArr<uint8_t> T;
+  BuildClock bc;
+  const unsigned nt = (unsigned)std::max(1, threads);
+  uint64_t tlen = 0;                              // == bwtlen of the file's own index
+  if (!read_fasta(faa, trans, nt, seqs, T, tlen)) return KAIJU_GPU_ERR_IO;
+  const uint64_t nseq = seqs.size();
+  bc.mark("read FASTA");
+  if (sizeof(I) == 4 && tlen >= 0xfffffff0ull) { g_err = "internal: index type too small"; return KAIJU_GPU_ERR_ARG; }
+
+  const uint64_t N = copies < 1 ? 1 : copies;
+  if (nseq * N >= 0x7fffffffull) { g_err = "too many sequences for the .fmi header (int32)"; return KAIJU_GPU_ERR_ARG; }
+  std::vector<uint64_t> starts(nseq), lens(nseq);
+  long maxlen = 0;
+  for (uint64_t i = 0; i < nseq; i++) { starts[i] = seqs[i].start; lens[i] = seqs[i].len; if ((long)seqs[i].len > maxlen) maxlen = (long)seqs[i].len; }
+  FmiArrays A;
+  A.P = fb_make_plan(tlen, nseq, (uint64_t)maxlen, N, chpt_exp);
+  if (stats) memset(stats, 0, sizeof *stats);
+
+  // ---- the suffix array of the letter suffixes (device_id >= 0: sorted on that GPU, libkaiju_mkfmi_gpu.so only), and the arrays
+  //      of the file from it (stages: on the host or, with the suffix array staying there, on the device) ------------------------
+#ifdef KAIJU_MKFMI_GPU
+  if (device_id >= 0 && stages == KAIJU_FMI_STAGES_DEVICE) {
+    const int rc = stages_device(T.data(), lens, device_id, 1, bc, A, stats);
+    if (rc != KAIJU_GPU_OK) return rc;
+  } else
+#endif
+  {
+    const uint64_t nsuf = tlen - nseq;
+    RawArr<I> SA(nsuf);
+    int rc;
+#ifdef KAIJU_MKFMI_GPU
+    if (device_id >= 0) rc = sort_suffixes_device<I>(T, tlen, nsuf, device_id, SA, bc, stats ? &stats->sort : nullptr);
+    else
+#endif
+      rc = sort_suffixes_host<I>(T, tlen, nsuf, nt, SA, bc);
+    if (rc == KAIJU_GPU_OK) rc = stages_host<I>(T.data(), starts, lens, SA, nt, 1, bc, A);
+    if (rc != KAIJU_GPU_OK) return rc;
+  }
+  const uint64_t otlen = A.P.otlen, onseq = A.P.onseq;          // what the output describes
+  const int sbits = A.P.sbits, pbits = A.P.pbits, nbytes = A.P.nbytes, N1 = A.P.N1, N2 = A.P.N2;
+  const int64_t ncheck = A.P.ncheck, bwtlen = (int64_t)otlen;
+  const int64_t mask = (1 << pbits) - 1, check = (1 << chpt_exp) - 1;
+  const std::vector<uint32_t> &read_of_rank = A.read_of_rank;
+  const RawArr<uint8_t> &sa = A.sa;
+  const uint8_t *bwt = A.bwt;
+  const std::vector<int64_t> &index1 = A.index1;
+  const RawArr<uint16_t> &index2 = A.index2;
+  const int *startLcode = A.startLcode;
+
   // ---- write the file (bwt.c:38-44, suffixArray.c:255-275, fmicommon.h:176-186, compactfmi.c:175-178)
   FILE *fp = fopen(out, "wb");
   if (!fp) { g_err = std::string("cannot write ") + out; return KAIJU_GPU_ERR_IO; }
@@ -610,7 +717,7 @@ namespace {
 // (KAIJU_MKFMI_FORCE64=1: the 64-bit instantiation on a small file - tests/test_mkfmi_pin.py)
 // (replicated: the FILE is sorted, so 32-bit suffix positions do as long as it has fewer than 4 G symbols)
 int build_any(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies, const uint64_t *copy_taxids,
-              uint32_t n_copy_taxids, int device_id) {
+              uint32_t n_copy_taxids, int device_id, int stages = KAIJU_FMI_STAGES_HOST, kaiju_fmi_build_stats *stats = nullptr) {
   if (!faa_path || !out_fmi_path || chpt_exp < 0 || chpt_exp > 20 || copies < 1 || (n_copy_taxids && !copy_taxids)) return KAIJU_GPU_ERR_ARG;
   if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
   FILE *fp = fopen(faa_path, "rb");
@@ -623,10 +730,65 @@ int build_any(const char *faa_path, const char *out_fmi_path, int threads, int c
     g_err = "suffix sort on the device: 32-bit positions only (file of " + std::to_string((uint64_t)sz) + " bytes); kaiju_build_fmi, the host builder, sorts with 64-bit positions";
     return KAIJU_GPU_ERR_ARG;
   }
-  if (narrow && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
-  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
+  if (narrow && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats);
+  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats);
+}
+
+// the arrays of a text (kaiju_fmi_arrays_*): sizes only, or the host / the device stages into the caller's buffers
+int arrays_any(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int threads, int device_id, int recode, kaiju_fmi_arrays *a,
+               kaiju_fmi_build_stats *stats, bool sizes_only) {
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (!text || !a || tlen == 0 || chpt_exp < 0 || chpt_exp > 20 || copies < 1) { g_err = "fmi arrays: bad argument"; return KAIJU_GPU_ERR_ARG; }
+  if (tlen >= 0xf0000000ull) { g_err = "fmi arrays: 32-bit positions only (text of " + std::to_string(tlen) + " symbols)"; return KAIJU_GPU_ERR_ARG; }
+  if (text[tlen - 1] != 0) { g_err = "fmi arrays: the text does not end with a terminator"; return KAIJU_GPU_ERR_ARG; }
+  std::vector<uint64_t> starts, lens;
+  uint64_t maxlen = 0;
+  for (uint64_t p = 0, b = 0; p < tlen; p++) {
+    if (text[p] > 20) { g_err = "fmi arrays: symbol codes are 0 .. 20"; return KAIJU_GPU_ERR_ARG; }
+    if (text[p] == 0) { starts.push_back(b); lens.push_back(p - b); maxlen = std::max(maxlen, p - b); b = p + 1; }
+  }
+  const uint64_t nseq = starts.size();
+  if (nseq * copies >= 0x7fffffffull || copies >= 0x7fffffffull) { g_err = "too many sequences for the .fmi header (int32)"; return KAIJU_GPU_ERR_ARG; }
+  FmiArrays A;
+  A.P = fb_make_plan(tlen, nseq, maxlen, copies, chpt_exp);
+  const FbPlan &P = A.P;
+  a->nseq = nseq; a->bwtlen = P.otlen; a->n_samples_bytes = fb_samples_bytes(P); a->n_index1 = (uint64_t)P.N1 * KJ_FB_ALEN; a->n_index2 = (uint64_t)P.N2 * KJ_FB_ALEN;
+  a->ncheck = P.ncheck; a->nbytes = P.nbytes; a->sbits = P.sbits; a->pbits = P.pbits; a->N1 = P.N1; a->N2 = P.N2; a->reserved = 0;
+  if (sizes_only) return KAIJU_GPU_OK;
+  if (!a->read_of_rank || !a->bwt || !a->index1 || !a->index2 || (a->n_samples_bytes && !a->samples)) { g_err = "fmi arrays: no buffers"; return KAIJU_GPU_ERR_ARG; }
+  BuildClock bc;
+  int rc;
+#ifdef KAIJU_MKFMI_GPU
+  if (device_id >= 0) rc = stages_device(text, lens, device_id, recode, bc, A, stats);
+  else
+#endif
+  {
+    const unsigned nt = (unsigned)(threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency()));
+    RawArr<uint8_t> T(tlen + 16);
+    memcpy(T.data(), text, (size_t)tlen);
+    memset(T.data() + tlen, 0, 16);                    // padding for the word-wise comparator
+    RawArr<uint32_t> SA(P.nsuf);
+    rc = sort_suffixes_host<uint32_t>(T, tlen, P.nsuf, nt, SA, bc);
+    if (rc == KAIJU_GPU_OK) rc = stages_host<uint32_t>(T.data(), starts, lens, SA, nt, recode, bc, A);
+  }
+  if (rc != KAIJU_GPU_OK) return rc;
+  if (nseq) memcpy(a->read_of_rank, A.read_of_rank.data(), (size_t)nseq * 4);
+  if (a->n_samples_bytes) memcpy(a->samples, A.sa.data(), (size_t)a->n_samples_bytes);
+  memcpy(a->bwt, A.bwt, (size_t)P.otlen);
+  memcpy(a->index1, A.index1.data(), (size_t)a->n_index1 * 8);
+  memcpy(a->index2, A.index2.data(), (size_t)a->n_index2 * 2);
+  for (int k = 0; k < 22; k++) a->startLcode[k] = A.startLcode[k];
+  return KAIJU_GPU_OK;
 }
 }  // namespace
+
+extern "C" int kaiju_fmi_arrays_sizes(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, kaiju_fmi_arrays *a) {
+  return arrays_any(text, tlen, copies, chpt_exp, 1, -1, 0, a, nullptr, true);
+}
+
+extern "C" int kaiju_fmi_arrays_host(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int threads, int recode, kaiju_fmi_arrays *a) {
+  return arrays_any(text, tlen, copies, chpt_exp, threads, -1, recode, a, nullptr, false);
+}
 
 extern "C" int kaiju_build_fmi(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp) {
   return build_any(faa_path, out_fmi_path, threads, chpt_exp, 1, nullptr, 0, -1);
@@ -647,6 +809,23 @@ extern "C" int kaiju_build_fmi_replicated_device(const char *faa_path, const cha
                                                  const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id) {
   const int rc = kj_sufsort_check_device(device_id, g_err);
   return rc != KAIJU_GPU_OK ? rc : build_any(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id);
+}
+
+extern "C" int kaiju_build_fmi_device_ex(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
+                                         const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id, int stages, kaiju_fmi_build_stats *stats) {
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (stages != KAIJU_FMI_STAGES_HOST && stages != KAIJU_FMI_STAGES_DEVICE) {
+    g_err = "stages = " + std::to_string(stages) + ": KAIJU_FMI_STAGES_HOST or KAIJU_FMI_STAGES_DEVICE";
+    return KAIJU_GPU_ERR_ARG;
+  }
+  const int rc = kj_sufsort_check_device(device_id, g_err);
+  return rc != KAIJU_GPU_OK ? rc : build_any(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats);
+}
+
+extern "C" int kaiju_fmi_arrays_device(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int device_id, int recode, kaiju_fmi_arrays *a,
+                                       kaiju_fmi_build_stats *stats) {
+  const int rc = kj_sufsort_check_device(device_id, g_err);
+  return rc != KAIJU_GPU_OK ? rc : arrays_any(text, tlen, copies, chpt_exp, 1, device_id, recode, a, stats, false);
 }
 
 extern "C" int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats) {

@@ -6,11 +6,14 @@
  * (tests/test_mkfmi_pin.py).  It is compiled into a library of its own, kaiju_amd/libkaiju_mkfmi.so (host only, no HIP);
  * libkaiju_gpu.so does not contain it.
  *
- * A third library, kaiju_amd/libkaiju_mkfmi_gpu.so, is the same builder compiled with -DKAIJU_MKFMI_GPU plus sufsort.hip: it
- * has every entry point of the host library and the *_device ones below, which sort the suffixes on a GPU (kj_sufsort.h) and
- * leave everything else - BWT, sequence ranks, SA samples, byte coding, checkpoints, the file - to the same host code, so the
- * file is byte for byte the host builder's (tests/test_gpu_sufsort.py).  The host library does not have the *_device entry
- * points and needs no HIP runtime.
+ * A third library, kaiju_amd/libkaiju_mkfmi_gpu.so, is the same builder compiled with -DKAIJU_MKFMI_GPU plus sufsort.hip and
+ * fmibuild.hip: it has every entry point of the host library and the *_device ones below, which sort the suffixes on a GPU
+ * (kj_sufsort.h) and by default leave everything else - BWT, sequence ranks, SA samples, byte coding, checkpoints, the file -
+ * to the same host code, so the file is byte for byte the host builder's (tests/test_gpu_sufsort.py).  Asked to
+ * (kaiju_build_fmi_device_ex with KAIJU_FMI_STAGES_DEVICE) they also run the stages behind the sort on the GPU (kj_fmibuild.h):
+ * text, ranks and suffix array stay in device memory, five passes make the arrays of the file there, the host downloads what it
+ * writes and writes it with the one copy of the header / names / write code - the same bytes again (tests/test_gpu_fmibuild.py).
+ * The host library does not have the *_device entry points and needs no HIP runtime.
  */
 #ifndef KAIJU_MKFMI_H
 #define KAIJU_MKFMI_H
@@ -62,6 +65,50 @@ int kaiju_build_fmi_replicated_device(const char *faa_path, const char *out_fmi_
    sa_out: room for tlen minus the number of terminators; *n_out: how many were written.  tlen >= 0xf0000000 is refused
    (KAIJU_GPU_ERR_ARG) before the text is looked at.  stats may be NULL. */
 int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats);
+
+
+/* ---- the arrays of a .fmi from a text, without a file (both libraries) ------------------------------------------------------
+   text[0, tlen): letter codes 1 .. 20 and a terminator 0 behind every sequence, the last symbol a terminator; `copies` and
+   chpt_exp as above.  kaiju_fmi_arrays_sizes fills the sizes of *a (everything above the pointers); the caller then points the
+   pointers at buffers of those sizes and calls kaiju_fmi_arrays_host, which sorts on the host and runs the host stages.
+   recode = 0 leaves the BWT letters raw (startLcode is computed all the same). */
+typedef struct kaiju_fmi_arrays {
+  uint64_t nseq, bwtlen;                           /* sequences of the text (not times copies); rows of the output = tlen * copies */
+  uint64_t n_samples_bytes, n_index1, n_index2;    /* ncheck * nbytes bytes; N1 * 21 int64; N2 * 21 uint16 */
+  int64_t ncheck;
+  int32_t nbytes, sbits, pbits, N1, N2, reserved;
+  uint32_t *read_of_rank;                          /* [nseq]: the file index of the sequence with sorted rank r */
+  uint8_t *samples;                                /* [n_samples_bytes], big-endian entries of nbytes */
+  uint8_t *bwt;                                    /* [bwtlen] */
+  int64_t *index1;                                 /* [n_index1] */
+  uint16_t *index2;                                /* [n_index2] */
+  int32_t startLcode[22];
+} kaiju_fmi_arrays;
+int kaiju_fmi_arrays_sizes(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, kaiju_fmi_arrays *a);
+int kaiju_fmi_arrays_host(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int threads, int recode, kaiju_fmi_arrays *a);
+
+/* ---- libkaiju_mkfmi_gpu.so only: the stages behind the sort on the device (kj_fmibuild.h, fmibuild.hip) ------------------------ */
+enum { KAIJU_FMI_STAGES_HOST = 0, KAIJU_FMI_STAGES_DEVICE = 1 };
+enum { KAIJU_FMI_STAGE_BWT = 1, KAIJU_FMI_STAGE_RANKS = 2, KAIJU_FMI_STAGE_SAMPLES = 4, KAIJU_FMI_STAGE_CHECKPOINTS = 8, KAIJU_FMI_STAGE_RECODE = 16 };
+typedef struct kaiju_fmi_build_stats {
+  uint32_t device_stages;                          /* KAIJU_FMI_STAGE_* of the stages that ran on the device; 0 with the host stages */
+  uint32_t reserved;
+  float ms_bwt, ms_ranks, ms_samples, ms_checkpoints, ms_recode;   /* HIP events around each pass (ms_samples: replication + samples) */
+  float ms_download;                               /* ... and around the download of read_of_rank, samples, index2 and BWT */
+  uint64_t device_bytes;                           /* what the size check compared with the free device memory */
+  kaiju_sufsort_stats sort;                        /* (ms_sort without a download: SA stays on the device) */
+} kaiju_fmi_build_stats;
+/* kaiju_build_fmi_replicated_device with a choice of where the stages behind the sort run.  KAIJU_FMI_STAGES_HOST: what
+   kaiju_build_fmi_replicated_device does.  KAIJU_FMI_STAGES_DEVICE: on the device; the same bytes.  Any other value:
+   KAIJU_GPU_ERR_ARG.  The device memory needed - the sort's scratch that is kept plus tlen * copies bytes of BWT, samples,
+   index2 and piece counts (kj_fmibuild.h: fb_scratch_bytes) - is compared with the free device memory before anything is
+   allocated: KAIJU_GPU_ERR_NOMEM with both numbers, and no output file.  stats may be NULL. */
+int kaiju_build_fmi_device_ex(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
+                              const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id, int stages, kaiju_fmi_build_stats *stats);
+/* kaiju_fmi_arrays_host with the sort and all five stages on device `device_id`: the analogue of kaiju_suffix_sort_device.
+   Host pointers, blocking.  stats may be NULL. */
+int kaiju_fmi_arrays_device(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int device_id, int recode, kaiju_fmi_arrays *a,
+                            kaiju_fmi_build_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -184,13 +184,32 @@ int kj_sufsort_check_device(int device_id, std::string &err) {
 
 int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
                       std::string &err) {
+  return kj_sufsort_device_keep(text, tlen, device_id, sa_out, n_out, stats, nullptr, err);
+}
+
+// what one sort allocates (the caller has selected the device: rocPRIM sizes its temporary storage for it)
+uint64_t kj_sufsort_need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t *temp_bytes_out) {
+  const uint64_t n = std::max<uint64_t>(nsuf, 1);
+  const uint64_t nlanes = (tlen + KJ_SS_LANE_BYTES - 1) / KJ_SS_LANE_BYTES, ntiles = (nlanes + KJ_SS_BLOCK - 1) / KJ_SS_BLOCK;
+  const uint64_t rank_entries = nlanes * KJ_SS_LANE_BYTES;
+  const unsigned round_bits = 32u + (unsigned)bits_of(tlen);
+  const size_t temp_bytes = std::max({sort_temp(n, KJ_SS_KEY_BITS), sort_temp(n, round_bits), scan64_temp(n), scan32_temp(n), tile_temp(ntiles)});
+  if (temp_bytes_out) *temp_bytes_out = temp_bytes;
+  return ss_scratch_bytes(tlen, nsuf) + 4 * (rank_entries - tlen) + temp_bytes + 4 * ntiles;
+}
+
+// keep != nullptr: SA is not downloaded (sa_out may be nullptr); text, rank[], SA, the first key buffer and the temporary
+// storage stay allocated and are handed to the caller, who frees them (hipFree) - also for a text without a suffix, whose
+// terminators still get their ranks
+int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                           SsKeep *keep, std::string &err) {
   if (stats) memset(stats, 0, sizeof *stats);
   if (n_out) *n_out = 0;
   if (!ss_tlen_ok(tlen)) {
     err = "suffix sort on the device: 32-bit positions only (text of " + std::to_string(tlen) + " symbols); kaiju_build_fmi, the host builder, sorts with 64-bit positions";
     return KAIJU_GPU_ERR_ARG;
   }
-  if (!text || tlen == 0 || (!sa_out && tlen)) { err = "suffix sort on the device: no text"; return KAIJU_GPU_ERR_ARG; }
+  if (!text || tlen == 0 || (!sa_out && !keep)) { err = "suffix sort on the device: no text"; return KAIJU_GPU_ERR_ARG; }
   if (text[tlen - 1] != 0) { err = "suffix sort on the device: the text does not end with a terminator"; return KAIJU_GPU_ERR_ARG; }
   int rc = kj_sufsort_check_device(device_id, err);
   if (rc != KAIJU_GPU_OK) return rc;
@@ -205,7 +224,7 @@ int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_
   }
   const uint64_t nsuf = tlen - nseq;
   if (n_out) *n_out = nsuf;
-  if (nsuf == 0) return KAIJU_GPU_OK;
+  if (nsuf == 0 && !keep) return KAIJU_GPU_OK;
 
   DeviceGuard dg;
   SS_HIP(hipGetDevice(&dg.prev));
@@ -214,8 +233,9 @@ int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_
   const uint64_t nlanes = (tlen + KJ_SS_LANE_BYTES - 1) / KJ_SS_LANE_BYTES, ntiles = (nlanes + KJ_SS_BLOCK - 1) / KJ_SS_BLOCK;
   const uint64_t text_bytes = ss_text_alloc(tlen), rank_entries = nlanes * KJ_SS_LANE_BYTES;
   const unsigned round_bits = 32u + (unsigned)bits_of(tlen);
-  const size_t temp_bytes = std::max({sort_temp(nsuf, KJ_SS_KEY_BITS), sort_temp(nsuf, round_bits), scan64_temp(nsuf), scan32_temp(nsuf), tile_temp(ntiles)});
-  const uint64_t need = ss_scratch_bytes(tlen, nsuf) + 4 * (rank_entries - tlen) + temp_bytes + 4 * ntiles;
+  uint64_t temp_bytes64 = 0;
+  const uint64_t need = kj_sufsort_need_bytes(tlen, nsuf, &temp_bytes64);
+  const size_t temp_bytes = (size_t)temp_bytes64;
   size_t free_b = 0, total_b = 0;
   SS_HIP(hipMemGetInfo(&free_b, &total_b));
   if (need > free_b) {
@@ -256,7 +276,7 @@ int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_
   rocprim::double_buffer<uint32_t> vb(d_v0.as<uint32_t>(), d_v1.as<uint32_t>());
   uint64_t m = nsuf, h = 0;
   uint32_t rounds = 0;
-  for (;;) {
+  while (m != 0) {                                          // (a text without a suffix, kept: no round)
     const int first = rounds == 0;
     if (stats && rounds < KJ_SS_STATS_ROUNDS) stats->active[rounds] = m;
     if (!first) {
@@ -295,11 +315,16 @@ int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_
   }
   k_ss_scatter<<<grid_for(nlanes), KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), d_rank.as<uint4>(), nlanes, (uint32_t)nseq, nsuf, d_v0.as<uint32_t>());
   SS_HIP(hipGetLastError());
-  SS_HIP(hipMemcpyAsync(sa_out, d_v0.p, 4 * nsuf, hipMemcpyDeviceToHost, st));
+  if (!keep) SS_HIP(hipMemcpyAsync(sa_out, d_v0.p, 4 * nsuf, hipMemcpyDeviceToHost, st));
   SS_HIP(hipEventRecord(ev.b, st));
   SS_HIP(hipStreamSynchronize(st));
   float ms = 0.f;
   SS_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
   if (stats) { stats->rounds = rounds; stats->ms_sort = ms; }
+  if (keep) {
+    keep->text = d_text.p; keep->rank = d_rank.p; keep->sa = d_v0.p; keep->k0 = d_k0.p; keep->temp = d_temp.p;
+    d_text.p = d_rank.p = d_v0.p = d_k0.p = d_temp.p = nullptr;
+    keep->temp_bytes = temp_bytes; keep->nseq = nseq; keep->nsuf = nsuf; keep->maxlen = maxlen; keep->bytes = need;
+  }
   return KAIJU_GPU_OK;
 }
