@@ -741,6 +741,83 @@ int kaiju_gpu_krona_text(kaiju_gpu_krona *k, kaiju_gpu_tally *const *tallies, ui
 enum { KAIJU_GPU_KRONA_PASSES = 5 };
 int kaiju_gpu_krona_pass_ms(kaiju_gpu_krona *k, float *ms, uint32_t n);
 
+/* ---- kaiju-convertNR: the accession map and the conversion of nr-style text ------------------------------------- */
+/* The accession -> taxon map of kaiju-convertNR.cpp:145-194, built and probed on the device (kaiju_amd/csrc/accmap.hip; the
+   rules: kj_convert.h): open addressing over 64-bit slots, the keys compacted into an arena of { line number, taxon, length,
+   key } entries, ~ 24 + the key rounded up to 8 bytes each.  The first line that inserts a key wins, whatever the order of the
+   lanes and however the file is cut into blocks.  Slots (rehash at a load of 1/2) and the arena grow on demand; every
+   allocation is checked against the free device memory first (KAIJU_GPU_ERR_NOMEM with both numbers).  Every probe loop is
+   bounded by the number of slots: a table that is full all the same is KAIJU_GPU_ERR_FORMAT, never a spin.
+   `tax` (it must outlive the map) and merged_pairs - n_merged pairs { old id, new id } of merged.dmp, the first pair of an old id
+   wins - decide which lines insert; tax == NULL makes a map for kaiju_gpu_accmap_add_keys only.  key_col / taxon_col: the columns
+   (from 0) of key and taxon; 1 and 2, the tool's, is what exists (KAIJU_GPU_ERR_UNSUPPORTED otherwise).  initial_slots is
+   rounded up to a power of two, at least 8 (0: 2^16). */
+typedef struct kaiju_gpu_accmap kaiju_gpu_accmap;
+int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, uint32_t key_col,
+                            uint32_t taxon_col, uint64_t initial_slots, kaiju_gpu_accmap **out);
+void kaiju_gpu_accmap_free(kaiju_gpu_accmap *m);
+/* A block of the map file, cut behind a line end (the last block need not end in one); is_first_block: its first line is the
+   file's header line and is skipped.  Blocks below 2^32 - 16 bytes.  The call blocks.  The _device form takes a 16-byte aligned
+   device pointer with 16 readable bytes behind the text. */
+int kaiju_gpu_accmap_add_text(kaiju_gpu_accmap *m, const char *text, uint64_t n, int is_first_block);
+int kaiju_gpu_accmap_add_text_device(kaiju_gpu_accmap *m, const void *d_text, uint64_t n, int is_first_block);
+/* Every non-empty line, whole, is a key with the value `value` (the excluded accessions of -e) */
+int kaiju_gpu_accmap_add_keys(kaiju_gpu_accmap *m, const char *text, uint64_t n, uint64_t value);
+/* Tests and diagnostics: the taxon of every line of `keys` (an empty line is the key of zero bytes) into taxa[0 .. min(lines, cap)),
+   KAIJU_GPU_ACCMAP_MISS for a key the map does not hold; *n_keys: the lines */
+#define KAIJU_GPU_ACCMAP_MISS (~0ull)
+int kaiju_gpu_accmap_lookup(kaiju_gpu_accmap *m, const char *keys, uint64_t n, uint64_t *taxa, uint64_t cap, uint64_t *n_keys);
+typedef struct kaiju_gpu_accmap_stats {
+  uint64_t entries;                /* distinct keys                                                                        */
+  uint64_t slots;
+  uint64_t arena_bytes, arena_cap; /* used (entries that lost a race for their slot included) / allocated                  */
+  uint64_t lines;                  /* non-empty lines seen, the header line not counted                                    */
+  uint64_t lines_no_insert;        /* ... that inserted nothing: ULONG_MAX, neither node nor merged to one                 */
+  uint64_t duplicates;             /* ... whose key another line had inserted                                              */
+  uint64_t rehashes;
+  uint64_t probe_hist[16];         /* entries by the slots a lookup of their key reads: 1, 2, .. 15, 16 or more            */
+  uint64_t reserved[8];
+} kaiju_gpu_accmap_stats;          /* 256 bytes */
+int kaiju_gpu_accmap_info(kaiju_gpu_accmap *m, kaiju_gpu_accmap_stats *out);
+/* With KAIJU_GPU_CONVERT_TIMES=1 at create: the milliseconds of the last add call's passes - lines, parse, grow, insert, resolve */
+enum { KAIJU_GPU_ACCMAP_PASSES = 5 };
+int kaiju_gpu_accmap_pass_ms(kaiju_gpu_accmap *m, float *ms, uint32_t n);
+
+/* What kaiju-convertNR.cpp:221-306 writes for a block of nr-style text (kaiju_amd/csrc/convert.hip; the rules: kj_convert.h):
+   per kept record '>' [first accession with a taxon '_'] taxon '\n' letters '\n', in the order of the text.  The block starts
+   at a header line or is the start of the file; the '\n' of a file of which nothing is kept is the caller's.  include_ids: the
+   ids of -l that are nodes (NULL with n_include 0: 2, 2157, 10239).  `map`, `excluded` (may be NULL) and `tax` must outlive the
+   converter; the maps may grow between calls.  On a taxonomy that is no single tree a record whose taxa have no common
+   ancestor is dropped and counted (the tool hangs or throws). */
+typedef struct kaiju_gpu_converter kaiju_gpu_converter;
+int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
+                               const kaiju_gpu_accmap *excluded, int add_acc, kaiju_gpu_converter **out);
+void kaiju_gpu_converter_free(kaiju_gpu_converter *c);
+typedef struct kaiju_gpu_convert_info {
+  uint64_t text_bytes;             /* of the whole output, also when it overflowed                                         */
+  uint64_t written_bytes;          /* of the whole records in front of out_cap                                             */
+  uint64_t n_records, n_kept;
+  uint64_t dropped_excluded;       /* an accession of the excluded set                                                     */
+  uint64_t dropped_no_taxon;       /* no accession with a taxon > 0                                                        */
+  uint64_t dropped_not_included;   /* no id of the include list above the taxon                                            */
+  uint64_t dropped_no_lca;         /* the taxa have no common ancestor: the tree is no tree                                */
+  uint64_t n_entries, n_hits;      /* entries of the headers / those the map holds with a taxon > 0                        */
+  uint64_t n_lines;
+  uint32_t overflow, reserved0;    /* 1: the text is longer than out_cap                                                   */
+  uint64_t reserved[4];
+} kaiju_gpu_convert_info;          /* 128 bytes */
+/* All pointers device pointers, d_text and d_out 16-byte aligned, 16 readable bytes behind the text, bytes <= 2^32 - 17; every
+   pass is queued on `stream` (NULL: a stream of the object), nothing synchronises.  A record is written whole or not at all
+   and no byte at or behind out_cap is touched.  One call at a time per object. */
+int kaiju_gpu_convert_text_device(kaiju_gpu_converter *c, const void *d_text, uint64_t bytes, void *d_out, uint64_t out_cap,
+                                  kaiju_gpu_convert_info *d_info, void *stream);
+/* The same from and into host memory; blocks */
+int kaiju_gpu_convert_text(kaiju_gpu_converter *c, const char *text, uint64_t bytes, char *out, uint64_t out_cap, kaiju_gpu_convert_info *info);
+/* With KAIJU_GPU_CONVERT_TIMES=1 at create: the milliseconds of the last call's passes - lines, kinds, entries, decide,
+   lengths and offsets, write, finish */
+enum { KAIJU_GPU_CONVERT_PASSES = 7 };
+int kaiju_gpu_convert_pass_ms(kaiju_gpu_converter *c, float *ms, uint32_t n);
+
 /* ---- the rows of kaiju2table (host only, no GPU) -------------------------------------------------------------- */
 enum { KAIJU_TABLE_EXPAND_VIRUSES = 1, KAIJU_TABLE_FILTER_UNCLASSIFIED = 2, KAIJU_TABLE_FULL_PATH = 4 };   /* -e, -u, -p */
 typedef struct kaiju_table_options {

@@ -100,6 +100,13 @@ KRONA_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("written_bytes", "<u8"), ("
                              ("n_unnamed_reads", "<u8"), ("n_unclassified", "<u8"), ("overflow", "<u4"), ("reserved", "<u4")])   # kaiju_gpu_krona_info
 assert KRONA_INFO_DTYPE.itemsize == 64
 KRONA_MAX_TALLIES, KRONA_PASSES = 4, 5
+ACCMAP_STATS_DTYPE = np.dtype([("entries", "<u8"), ("slots", "<u8"), ("arena_bytes", "<u8"), ("arena_cap", "<u8"), ("lines", "<u8"), ("lines_no_insert", "<u8"),
+                               ("duplicates", "<u8"), ("rehashes", "<u8"), ("probe_hist", "<u8", (16,)), ("reserved", "<u8", (8,))])   # kaiju_gpu_accmap_stats
+CONVERT_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("written_bytes", "<u8"), ("n_records", "<u8"), ("n_kept", "<u8"), ("dropped_excluded", "<u8"),
+                               ("dropped_no_taxon", "<u8"), ("dropped_not_included", "<u8"), ("dropped_no_lca", "<u8"), ("n_entries", "<u8"), ("n_hits", "<u8"),
+                               ("n_lines", "<u8"), ("overflow", "<u4"), ("reserved0", "<u4"), ("reserved", "<u8", (4,))])   # kaiju_gpu_convert_info
+assert ACCMAP_STATS_DTYPE.itemsize == 256 and CONVERT_INFO_DTYPE.itemsize == 128
+ACCMAP_MISS, ACCMAP_PASSES, CONVERT_PASSES = 2 ** 64 - 1, 5, 7
 TABLE_EXPAND_VIRUSES, TABLE_FILTER_UNCLASSIFIED, TABLE_FULL_PATH = 1, 2, 4
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
@@ -255,6 +262,20 @@ def lib():
         L.kaiju_gpu_krona_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.kaiju_gpu_krona_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_krona_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "kaiju_gpu_accmap_create"):                 # (likewise)
+        L.kaiju_gpu_accmap_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_accmap_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_accmap_add_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.kaiju_gpu_accmap_add_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.kaiju_gpu_accmap_add_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.kaiju_gpu_accmap_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_accmap_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_accmap_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.kaiju_gpu_converter_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.kaiju_gpu_converter_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_convert_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_convert_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_convert_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     if hasattr(L, "kaiju_table_rows"):
         L.kaiju_table_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TableOptions), C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -760,6 +781,134 @@ class Krona:
     def close(self):
         if self._h:
             lib().kaiju_gpu_krona_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AccMap:
+    """The accession -> taxon map of kaiju-convertNR on the device (kaiju_gpu_accmap_create).  dtax: the tree whose nodes decide
+    which lines insert (None: a map for add_keys only, the excluded accessions); merged: (old id, new id) pairs of merged.dmp in
+    file order."""
+
+    def __init__(self, dtax=None, merged=(), device=0, initial_slots=0, key_col=1, taxon_col=2):
+        if not hasattr(lib(), "kaiju_gpu_accmap_create"):
+            raise KaijuGpuError("this library was linked without accmap.hip")
+        self._tax = dtax                                      # (the tree must outlive the map)
+        self._h = C.c_void_p()
+        pairs = np.array([x for p in merged for x in p], dtype=np.uint64)
+        _check(lib().kaiju_gpu_accmap_create(dtax._h if dtax is not None else None, device, pairs.ctypes.data if len(pairs) else None, len(pairs) // 2,
+                                             key_col, taxon_col, initial_slots, C.byref(self._h)))
+
+    def add_text(self, text: bytes, first_block=True):
+        """a block of the map file, cut behind a line end; first_block: its first line is the file's header line"""
+        _check(lib().kaiju_gpu_accmap_add_text(self._h, text, len(text), 1 if first_block else 0))
+        return self
+
+    def add_text_device(self, d_text_ptr: int, nbytes: int, first_block=True):
+        _check(lib().kaiju_gpu_accmap_add_text_device(self._h, d_text_ptr or None, nbytes, 1 if first_block else 0))
+
+    def add_keys(self, text: bytes, value=1):
+        """every non-empty line is a key with the value ``value``"""
+        _check(lib().kaiju_gpu_accmap_add_keys(self._h, text, len(text), value))
+        return self
+
+    def lookup(self, keys):
+        """the taxa of ``keys`` (a list of bytes without '\n'; ACCMAP_MISS: not in the map)"""
+        keys = list(keys)
+        if not keys:
+            return []
+        text = b"\n".join(keys) + b"\n"
+        out = np.zeros(len(keys) + 1, dtype=np.uint64)
+        n = C.c_uint64()
+        _check(lib().kaiju_gpu_accmap_lookup(self._h, text, len(text), out.ctypes.data, len(out), C.byref(n)))
+        assert n.value == len(keys), (n.value, len(keys))
+        return [int(x) for x in out[:len(keys)]]
+
+    def info(self):
+        out = np.zeros(1, dtype=ACCMAP_STATS_DTYPE)
+        _check(lib().kaiju_gpu_accmap_info(self._h, out.ctypes.data))
+        return out[0]
+
+    def pass_ms(self):
+        """milliseconds of the last add call's passes (lines, parse, grow, insert, resolve); needs KAIJU_GPU_CONVERT_TIMES=1 at creation"""
+        ms = np.zeros(ACCMAP_PASSES, dtype=np.float32)
+        _check(lib().kaiju_gpu_accmap_pass_ms(self._h, ms.ctypes.data, ACCMAP_PASSES))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_accmap_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Converter:
+    """kaiju-convertNR on blocks of nr-style text (kaiju_gpu_converter_create): per kept record '>' [accession '_'] taxon '\n'
+    letters '\n'.  include: the ids of -l that are nodes (None: 2, 2157, 10239); excluded: an AccMap built with add_keys."""
+
+    def __init__(self, dtax, amap: AccMap, excluded: AccMap = None, include=None, add_acc=False):
+        if not hasattr(lib(), "kaiju_gpu_converter_create"):
+            raise KaijuGpuError("this library was linked without convert.hip")
+        self._keep = (dtax, amap, excluded)                   # (they must outlive the converter)
+        self._h = C.c_void_p()
+        ids = np.array(list(include) if include is not None else [], dtype=np.uint64)
+        if include is not None and not len(ids):
+            ids = np.array([2 ** 64 - 1], dtype=np.uint64)   # an empty list keeps nothing: an id that is never a node
+        _check(lib().kaiju_gpu_converter_create(dtax._h, ids.ctypes.data if include is not None else None, len(ids) if include is not None else 0, amap._h,
+                                                excluded._h if excluded is not None else None, 1 if add_acc else 0, C.byref(self._h)))
+
+    def convert(self, text: bytes, out_cap=None):
+        """Returns (bytes, info): the records of a block that starts at a header line (or is the start of the file) and a
+        CONVERT_INFO_DTYPE record.  out_cap: the capacity (default: the size of the text, found by a call with none); when the
+        text overflows it only whole records in front of it are written"""
+        info = np.zeros(1, dtype=CONVERT_INFO_DTYPE)
+        if out_cap is None:
+            _check(lib().kaiju_gpu_convert_text(self._h, text, len(text), None, 0, info.ctypes.data))
+            out_cap = int(info[0]["text_bytes"])
+        cap = int(out_cap)
+        out = np.full(cap + 32, 0x77, dtype=np.uint8)
+        _check(lib().kaiju_gpu_convert_text(self._h, text, len(text), out.ctypes.data if cap else None, cap, info.ctypes.data))
+        assert (out[cap:] == 0x77).all()
+        return bytes(out[:int(info[0]["written_bytes"])]), info[0]
+
+    def convert_device(self, d_text_ptr: int, nbytes: int, d_out_ptr: int, out_cap: int, d_info_ptr: int, stream: int = 0):
+        """the same from and into device memory (raw pointers, 16-byte aligned): asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_convert_text_device(self._h, d_text_ptr or None, nbytes, d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def convert_file(self, text: bytes, block_bytes=1 << 24) -> bytes:
+        """a whole nr text, cut at "\n>" into blocks of about block_bytes: the tool's file, the '\n' of an empty one included"""
+        out, at = [], 0
+        while at < len(text):
+            end = len(text)
+            if end - at > block_bytes:
+                end = text.rfind(b"\n>", at, at + block_bytes) + 1
+                if end <= at:
+                    raise KaijuGpuError("a record of more than %d bytes" % block_bytes)
+            out.append(self.convert(text[at:end])[0])
+            at = end
+        got = b"".join(out)
+        return got if got else b"\n"
+
+    def pass_ms(self):
+        """milliseconds of the last call's passes (lines, kinds, entries, decide, lengths and offsets, write, finish); needs
+        KAIJU_GPU_CONVERT_TIMES=1 at creation"""
+        ms = np.zeros(CONVERT_PASSES, dtype=np.float32)
+        _check(lib().kaiju_gpu_convert_pass_ms(self._h, ms.ctypes.data, CONVERT_PASSES))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_converter_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
