@@ -818,6 +818,41 @@ int kaiju_gpu_convert_text(kaiju_gpu_converter *c, const char *text, uint64_t by
 enum { KAIJU_GPU_CONVERT_PASSES = 7 };
 int kaiju_gpu_convert_pass_ms(kaiju_gpu_converter *c, float *ms, uint32_t n);
 
+/* ---- kaiju-gbk2faa: GenBank flat files to the protein FASTA of the index builder ---------------------------------- */
+/* What util/kaiju-gbk2faa.pl writes for a block of GenBank flat-file text (kaiju_amd/csrc/gbk.hip; the rules: kj_gbk.h): per
+   /translation a header line '>' protein id '_' taxon '\n' and one line of filtered letters per line of the translation.  A
+   file is converted in blocks cut behind a '\n'; the object keeps what the script carries from line to line - the taxon and the
+   protein id seen last, whether a translation is open - in device memory between calls.  kaiju_gpu_gbk_reset starts a new file. */
+typedef struct kaiju_gpu_gbk kaiju_gpu_gbk;
+int kaiju_gpu_gbk_create(int device_id, kaiju_gpu_gbk **out);
+void kaiju_gpu_gbk_free(kaiju_gpu_gbk *g);
+int kaiju_gpu_gbk_reset(kaiju_gpu_gbk *g);
+typedef struct kaiju_gpu_gbk_info {
+  uint64_t text_bytes;             /* of the whole output, also when it overflowed                                         */
+  uint64_t written_bytes;          /* of the whole output lines in front of out_cap                                        */
+  uint64_t n_lines;
+  uint64_t lines_kind[5];          /* taxon, protein id, whole translation, translation opens, every other line            */
+  uint64_t n_records;              /* headers                                                                              */
+  uint64_t letters_kept, letters_dropped;   /* bytes of the printed spans the filter kept / dropped                        */
+  uint64_t no_taxon_line;          /* line (from 1, of this text) of the first /translation in front of which no taxon was */
+                                   /* seen, 0: none.  The script ends there with an empty file: nothing is written and the */
+                                   /* sizes, records and letters are 0                                                     */
+  uint32_t overflow, reserved0;    /* 1: the text is longer than out_cap                                                   */
+  uint64_t reserved[3];
+} kaiju_gpu_gbk_info;              /* 128 bytes */
+/* All pointers device pointers, d_text and d_out 16-byte aligned, 16 readable bytes behind the text, bytes <= 2^32 - 17; every
+   pass is queued on `stream` (NULL: a stream of the object), nothing synchronises unless scratch has to grow.  An output line is
+   written whole or not at all and no byte at or behind out_cap is touched.  A call that overflows or reports no_taxon_line
+   leaves the carried state as it was: the caller repeats it with text_bytes of room.  One call at a time per object. */
+int kaiju_gpu_gbk_text_device(kaiju_gpu_gbk *g, const void *d_text, uint64_t bytes, void *d_out, uint64_t out_cap, kaiju_gpu_gbk_info *d_info,
+                              void *stream);
+/* The same from and into host memory; blocks */
+int kaiju_gpu_gbk_text(kaiju_gpu_gbk *g, const char *text, uint64_t bytes, char *out, uint64_t out_cap, kaiju_gpu_gbk_info *info);
+/* With KAIJU_GPU_CONVERT_TIMES=1 at create: the milliseconds of the last call's passes - lines, kinds, scans, lengths and
+   offsets, write, finish */
+enum { KAIJU_GPU_GBK_PASSES = 6 };
+int kaiju_gpu_gbk_pass_ms(kaiju_gpu_gbk *g, float *ms, uint32_t n);
+
 /* ---- the rows of kaiju2table (host only, no GPU) -------------------------------------------------------------- */
 enum { KAIJU_TABLE_EXPAND_VIRUSES = 1, KAIJU_TABLE_FILTER_UNCLASSIFIED = 2, KAIJU_TABLE_FULL_PATH = 4 };   /* -e, -u, -p */
 typedef struct kaiju_table_options {

@@ -107,6 +107,10 @@ CONVERT_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("written_bytes", "<u8"), 
                                ("n_lines", "<u8"), ("overflow", "<u4"), ("reserved0", "<u4"), ("reserved", "<u8", (4,))])   # kaiju_gpu_convert_info
 assert ACCMAP_STATS_DTYPE.itemsize == 256 and CONVERT_INFO_DTYPE.itemsize == 128
 ACCMAP_MISS, ACCMAP_PASSES, CONVERT_PASSES = 2 ** 64 - 1, 5, 7
+GBK_INFO_DTYPE = np.dtype([("text_bytes", "<u8"), ("written_bytes", "<u8"), ("n_lines", "<u8"), ("lines_kind", "<u8", (5,)), ("n_records", "<u8"), ("letters_kept", "<u8"),
+                           ("letters_dropped", "<u8"), ("no_taxon_line", "<u8"), ("overflow", "<u4"), ("reserved0", "<u4"), ("reserved", "<u8", (3,))])   # kaiju_gpu_gbk_info
+assert GBK_INFO_DTYPE.itemsize == 128
+GBK_PASSES = 6
 TABLE_EXPAND_VIRUSES, TABLE_FILTER_UNCLASSIFIED, TABLE_FULL_PATH = 1, 2, 4
 assert SEG_FRAGMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 184 and RESULT_DTYPE.itemsize == 16 and COMPACT_DTYPE.itemsize == 16
@@ -276,6 +280,13 @@ def lib():
         L.kaiju_gpu_convert_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.kaiju_gpu_convert_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_convert_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "kaiju_gpu_gbk_create"):                    # (likewise)
+        L.kaiju_gpu_gbk_create.argtypes = [C.c_int, C.c_void_p]
+        L.kaiju_gpu_gbk_free.argtypes = [C.c_void_p]
+        L.kaiju_gpu_gbk_reset.argtypes = [C.c_void_p]
+        L.kaiju_gpu_gbk_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kaiju_gpu_gbk_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_gbk_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     if hasattr(L, "kaiju_table_rows"):
         L.kaiju_table_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TableOptions), C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.kaiju_gpu_get_op_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -909,6 +920,86 @@ class Converter:
     def close(self):
         if self._h:
             lib().kaiju_gpu_converter_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GbkNoTaxon(KaijuGpuError):
+    """a /translation in front of which the file has no /db_xref="taxon:..": kaiju-gbk2faa.pl ends there with an empty file"""
+
+    def __init__(self, line):
+        super().__init__("No taxon id found in gbk file (line %d)" % line)
+        self.line = line
+
+
+class Gbk:
+    """kaiju-gbk2faa on blocks of GenBank flat-file text (kaiju_gpu_gbk_create): per /translation a header '>' protein id '_' taxon
+    and a line of filtered letters per line of the translation.  The object carries the taxon and the protein id seen last and
+    whether a translation is open from block to block; reset() starts a new file."""
+
+    def __init__(self, device=0):
+        if not hasattr(lib(), "kaiju_gpu_gbk_create"):
+            raise KaijuGpuError("this library was linked without gbk.hip")
+        self._h = C.c_void_p()
+        _check(lib().kaiju_gpu_gbk_create(device, C.byref(self._h)))
+
+    def reset(self):
+        _check(lib().kaiju_gpu_gbk_reset(self._h))
+        return self
+
+    def convert(self, text: bytes, out_cap=None, fill=0x77):
+        """Returns (bytes, info): the output of a block that ends behind a line end (or is the end of the file) and a
+        GBK_INFO_DTYPE record.  out_cap: the capacity; when the text overflows only whole lines in front of it are written and
+        the carried state stays where it was.  Default: as much as the text has bytes, and the call is repeated with the
+        size the first one reported if that was too little (a header may be longer than its line)"""
+        info = np.zeros(1, dtype=GBK_INFO_DTYPE)
+        cap = len(text) if out_cap is None else int(out_cap)
+        while True:
+            out = np.full(cap + 32, fill, dtype=np.uint8)
+            _check(lib().kaiju_gpu_gbk_text(self._h, text, len(text), out.ctypes.data if cap else None, cap, info.ctypes.data))
+            assert (out[cap:] == fill).all()
+            if out_cap is not None or not info[0]["overflow"]:
+                return bytes(out[:int(info[0]["written_bytes"])]), info[0]
+            cap = int(info[0]["text_bytes"])
+
+    def convert_device(self, d_text_ptr: int, nbytes: int, d_out_ptr: int, out_cap: int, d_info_ptr: int, stream: int = 0):
+        """the same from and into device memory (raw pointers, 16-byte aligned): asynchronous on ``stream``"""
+        _check(lib().kaiju_gpu_gbk_text_device(self._h, d_text_ptr or None, nbytes, d_out_ptr or None, out_cap, d_info_ptr or None, stream or None))
+
+    def convert_file(self, text: bytes, block_bytes=1 << 24) -> bytes:
+        """a whole flat file, cut behind line ends into blocks of at most block_bytes: the script's file.  GbkNoTaxon (with the
+        line of the file) where the script dies"""
+        self.reset()
+        out, at, lines = [], 0, 0
+        while at < len(text):
+            end = len(text)
+            if end - at > block_bytes:
+                end = text.rfind(b"\n", at, at + block_bytes) + 1
+                if end <= at:
+                    raise KaijuGpuError("a line of more than %d bytes" % block_bytes)
+            got, info = self.convert(text[at:end])
+            if info["no_taxon_line"]:
+                raise GbkNoTaxon(lines + int(info["no_taxon_line"]))
+            out.append(got)
+            lines += int(info["n_lines"])
+            at = end
+        return b"".join(out)
+
+    def pass_ms(self):
+        """milliseconds of the last call's passes (lines, kinds, scans, lengths and offsets, write, finish); needs
+        KAIJU_GPU_CONVERT_TIMES=1 at creation"""
+        ms = np.zeros(GBK_PASSES, dtype=np.float32)
+        _check(lib().kaiju_gpu_gbk_pass_ms(self._h, ms.ctypes.data, GBK_PASSES))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().kaiju_gpu_gbk_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

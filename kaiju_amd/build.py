@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkaiju_gpu.so")
-SOURCES = ["capi.hip", "capi_index.hip", "capi_text.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "annotate.hip", "merge.hip", "tally.hip", "krona.hip", "accmap.hip", "convert.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
-HEADERS = ["capi_internal.h", "kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "kj_annotate.h", "kj_merge.h", "kj_tally.h", "kj_krona.h", "kj_convert.h", "kj_textlines.h", os.path.join("host", "table_rows.h"), "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
+SOURCES = ["capi.hip", "capi_index.hip", "capi_text.hip", "fmi_stream.hip", "exact_pass.hip", "ingest.hip", "format.hip", "format_verbose.hip", "format_seq.hip", "format_names.hip", "annotate.hip", "merge.hip", "tally.hip", "krona.hip", "accmap.hip", "convert.hip", "gbk.hip", "taxon_names.cpp", "accessions.cpp", "host_index.cpp", "host_tables.cpp", "taxonomy.cpp", "rccl_gather.cpp"]
+HEADERS = ["capi_internal.h", "kj_core.h", "kj_flow.h", "kj_rowtax_plan.h", "kj_greedy3.h", "fmi_stream.h", "exact_pass.h", "kj_ingest.h", "kj_format.h", "kj_format_verbose.h", "kj_format_seq.h", "kj_format_names.h", "kj_annotate.h", "kj_merge.h", "kj_tally.h", "kj_krona.h", "kj_convert.h", "kj_gbk.h", "kj_textlines.h", os.path.join("host", "table_rows.h"), "taxon_names.h", "kj_scan.h", "kj_lines.h", "host_index.h", "host_tables.h", os.path.join("..", "..", "include", "kaiju_gpu.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-gpu-rdc", "-Wno-unused-result"]
 
@@ -77,6 +77,7 @@ def build(force=False, verbose=False):
     build_table_cli(force=force, verbose=verbose)
     build_krona_cli(force=force, verbose=verbose)
     build_convert_cli(force=force, verbose=verbose)
+    build_gbk_cli(force=force, verbose=verbose)
     return LIB
 
 
@@ -183,6 +184,22 @@ def build_convert_cli(force=False, verbose=False):
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
     return CONVERT_CLI
+
+
+GBK_SRC = [os.path.join(CSRC, "host", f) for f in ("gbk_main.cpp", "gbk_blocks.h", "pargz.h")]
+GBK_CLI = os.path.join(HERE, "bin", "kaiju-gbk2faa")
+
+
+def build_gbk_cli(force=False, verbose=False):
+    """the drop-in `kaiju-gbk2faa` command (host C++ over the C-ABI)"""
+    if not force and os.path.exists(GBK_CLI) and os.path.getmtime(GBK_CLI) >= max([os.path.getmtime(LIB)] + [os.path.getmtime(s) for s in GBK_SRC]):
+        return GBK_CLI
+    os.makedirs(os.path.dirname(GBK_CLI), exist_ok=True)
+    cmd = ["g++", "-O2", "-std=c++17", "-o", GBK_CLI, GBK_SRC[0], "-L" + HERE, "-lkaiju_gpu", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return GBK_CLI
 
 
 if __name__ == "__main__":
