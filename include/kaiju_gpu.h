@@ -316,6 +316,25 @@ int kaiju_gpu_seg_regions(kaiju_gpu_ctx *ctx, const char *seqs, const uint64_t *
    read when an index is loaded, makes the SEG kernels of that index compute every window directly; the check still runs. */
 int kaiju_gpu_seg_table_check(const kaiju_gpu_index *index, uint64_t *entries, uint64_t *mismatches);
 
+/* Diagnostics: the rule by which the Greedy lane leaves a substitution variant on a few database rows unqueued
+   (kj_chain_hopeless), by itself.  A case is what the lane hands the rule: its window of the fragment (win[0] is
+   fragment position wq; KAIJU_GPU_CHAIN_WIN bytes - the 64 letters of the window and the slack of the lane's row behind them),
+   the variant's match [pz, j] of the fragment, tx = the 16 bytes of database text in front of the match (tx[15] next to it),
+   nmm substitutions made so far, sc0 the match's score, thr the score that matters, and the parameters m (min_fragment_length)
+   and mismatches.  One kernel, one lane per case, writes out[i] = 1 where the rule says that no item of the chain can hold a
+   match of m letters that scores thr, else 0.  No index and no context are needed.  Cases the lane cannot pass (wq < 0, pz < 0,
+   j < pz, pz - wq > 63, positions above 65535, mismatches > 8, nmm > mismatches) and more than 2^24 cases give
+   KAIJU_GPU_ERR_ARG.  The call blocks; it runs on `device` and leaves the calling thread's current device as it found it. */
+#define KAIJU_GPU_CHAIN_WIN 68
+typedef struct {
+  uint8_t win[KAIJU_GPU_CHAIN_WIN];
+  uint8_t tx[16];
+  int32_t wq, pz, j;
+  int32_t sc0, thr;
+  uint32_t nmm, m, mismatches;
+} kaiju_gpu_chain_case;
+int kaiju_gpu_chain_hopeless_check(int device, const kaiju_gpu_chain_case *cases, uint32_t n_cases, uint8_t *out);
+
 /* Diagnostics: the locate by itself.  Record r is given the suffix-array intervals first[r] .. first[r + 1] - 1 (at most 16:
    rows lo[i] .. lo[i] + len[i] - 1, len[i] >= 1) as the matches a search lane would have left in it, and the call runs the
    locate that a classification of this context would run on this index (the row -> taxon table, the sampled one, or the walk

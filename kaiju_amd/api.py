@@ -314,6 +314,22 @@ def device_count() -> int:
     return lib().kaiju_gpu_device_count()
 
 
+CHAIN_WIN = 68                     # KAIJU_GPU_CHAIN_WIN
+CHAIN_CASE_DTYPE = np.dtype([("win", "u1", (CHAIN_WIN,)), ("tx", "u1", (16,)), ("wq", "<i4"), ("pz", "<i4"), ("j", "<i4"), ("sc0", "<i4"),
+                             ("thr", "<i4"), ("nmm", "<u4"), ("m", "<u4"), ("mismatches", "<u4")])   # kaiju_gpu_chain_case
+assert CHAIN_CASE_DTYPE.itemsize == 116
+
+
+def chain_hopeless_check(cases, device: int = 0) -> np.ndarray:
+    """kaiju_gpu_chain_hopeless_check: the Greedy lane's pruning rule on the device, one answer byte per case (CHAIN_CASE_DTYPE)"""
+    L = lib()
+    L.kaiju_gpu_chain_hopeless_check.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    cases = np.ascontiguousarray(cases, dtype=CHAIN_CASE_DTYPE)
+    out = np.zeros(len(cases), dtype=np.uint8)
+    _check(L.kaiju_gpu_chain_hopeless_check(device, cases.ctypes.data, len(cases), out.ctypes.data))
+    return out
+
+
 IDS_TAXON, IDS_SEQUENCE = 0, 1     # kaiju_gpu_index_load_ex
 U_RULE_NUCLEOTIDE, U_RULE_PROTEIN = 0, 1     # KAIJU_GPU_U_RULE_*: which unclassified reads of kaijux / kaijup get a third column
 

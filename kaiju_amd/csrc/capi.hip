@@ -1745,6 +1745,60 @@ extern "C" int kaiju_gpu_seg_table_check(const kaiju_gpu_index *ix, uint64_t *en
   });
 }
 
+// Diagnostics: greedy_lane2's pruning rule by itself (include/kaiju_gpu.h): one lane per case calls kj_chain_hopeless - the
+// device's compilation of it - on a window row of the lane's own shape (kGWinStride words of LDS: kWin letters and the slack
+// behind them).  No index, no context: the kernel reads the cases and writes one byte each.
+static_assert(sizeof(kaiju_gpu_chain_case) == 116 && sizeof(kaiju_gpu_chain_case) % 4 == 0 && KAIJU_GPU_CHAIN_WIN == kGWinStride * 4 &&
+              KAIJU_GPU_CHAIN_WIN >= kWin + 4, "kaiju_gpu_chain_case holds a window row of the Greedy lane");
+__global__ void __launch_bounds__(256)
+k_chain_hopeless_check(const kaiju_gpu_chain_case *__restrict__ cases, uint32_t n, uint8_t *__restrict__ out) {
+  __shared__ uint32_t s_win[256 * kGWinStride];
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const kaiju_gpu_chain_case &c = cases[r];
+  uint32_t *row = s_win + threadIdx.x * kGWinStride;
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(c.win);
+  for (int x = 0; x < kGWinStride; x++) row[x] = src[x];
+  Params p{};
+  p.m = c.m; p.mismatches = c.mismatches;
+  u128 tx;
+  const uint32_t *t32 = reinterpret_cast<const uint32_t *>(c.tx);
+  tx.x = t32[0] | (uint64_t)t32[1] << 32; tx.y = t32[2] | (uint64_t)t32[3] << 32;
+  out[r] = kj_chain_hopeless(p, reinterpret_cast<const uint8_t *>(row), c.wq, c.pz, c.j, tx, c.nmm, c.sc0, c.thr) ? 1 : 0;
+}
+extern "C" int kaiju_gpu_chain_hopeless_check(int device, const kaiju_gpu_chain_case *cases, uint32_t n_cases, uint8_t *out) {
+  return guarded([&]() -> int {
+  if (int rc = no_device()) return rc;
+  if ((!cases || !out) && n_cases) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+  if (n_cases > (1u << 24)) return fail(KAIJU_GPU_ERR_ARG, "more than 2^24 cases");
+  for (uint32_t r = 0; r < n_cases; r++) {
+    // what the lane guarantees (GB_VAR_MATCH: pz is in the window, the match starts at pz): the rule's loads stay in the row
+    const kaiju_gpu_chain_case &c = cases[r];
+    if (c.wq < 0 || c.pz < 0 || c.pz > 0xffff || c.j < c.pz || c.j > 0xffff || c.pz - c.wq >= kWin || c.mismatches > (uint32_t)kMaxMismatch ||
+        c.nmm > c.mismatches)
+      return fail(KAIJU_GPU_ERR_ARG, "a case outside what the Greedy lane can pass");
+  }
+  if (n_cases == 0) return KAIJU_GPU_OK;
+  int prev = 0;                                    // (the calling thread's device is the caller's: put back before returning)
+  KJ_HIP(hipGetDevice(&prev));
+  KJ_HIP(hipSetDevice(device));
+  uint8_t *buf = nullptr;
+  const size_t in_bytes = (size_t)n_cases * sizeof(kaiju_gpu_chain_case);
+  hipError_t e = hipMalloc((void **)&buf, in_bytes + n_cases);
+  if (e == hipSuccess) e = hipMemcpy(buf, cases, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_chain_hopeless_check, dim3((n_cases + 255) / 256), dim3(256), 0, 0,
+                       reinterpret_cast<const kaiju_gpu_chain_case *>(buf), n_cases, buf + in_bytes);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, buf + in_bytes, n_cases, hipMemcpyDeviceToHost);
+  if (buf) (void)hipFree(buf);
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) return fail(KAIJU_GPU_ERR_HIP, hipGetErrorString(e));
+  return KAIJU_GPU_OK;
+  });
+}
+
 // Diagnostics: what the device SEG pass computed for every fragment of a batch of protein reads (include/kaiju_gpu.h).
 // Stage 1 (k_fragments_protein) and the SEG launch of launch_batch - launch_seg, or k_redo_seg with the exact pass's scratch -
 // on the buffers launch_batch uses; no search.  Blocking.

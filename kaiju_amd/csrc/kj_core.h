@@ -4331,9 +4331,10 @@ constexpr bool kChainPrune = true;
 // while the letters agree (UpdateSI on one row, bwt.c:160-173), a substitution (:346-395) takes the text's letter at a letter
 // that differs and costs one of the p.mismatches, and the item dies at the next difference once they are spent (:443-449).  So
 // the longest match the chain can reach ends in front of the (allowed + 1)-th difference - a matter of the MASK of differences
-// between the sixteen letters in front of the match on both sides, no loop, no score.  Scores, thresholds, terminators and the
-// order of the queue can only end the chain earlier.  tx: text[tp - 16, tp) of the match's text position tp; win / wq: the
-// lane's window of the fragment (the letters in front of pz are the fragment's own: a chain substitutes from right to left).
+// between the sixteen letters in front of the match on both sides, no loop, no score.  A text byte that is no letter (a
+// terminator) ends the chain too: nothing substitutes it.  Scores, thresholds and the order of the queue can only end the
+// chain earlier.  tx: text[tp - 16, tp) of the match's text position tp; win / wq: the lane's window of the fragment (the
+// letters in front of pz are the fragment's own: a chain substitutes from right to left).
 // Conservative: what it cannot see (letters in front of the window, a chain longer than sixteen letters) counts as reachable.
 // sc0: the score of the item's own match (eval_match_scores' m_dsum + diff).  A letter the chain gains adds at most 11 to it
 // (the largest entry of the BLOSUM62 diagonal: W), a substitution at most kMaxSubstScore (the largest entry off the diagonal;
@@ -4380,16 +4381,28 @@ KJ_HD bool kj_chain_hopeless(const Params &p, const uint8_t *win, int wq, int pz
   };
   // mask of differences by distance: byte 15 - k of f ^ tx <-> bit k
   const uint32_t mx = diff_bits(f.x ^ tx.x), my = diff_bits(f.y ^ tx.y);      // bit i <-> byte i (low half), byte 8 + i (high half)
-  uint32_t m16 = 0;
+  uint32_t m16 = 0, z16 = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
   m16 = (__brev(my) >> 24) | (__brev(mx) >> 24) << 8;
 #else
   for (int i = 0; i < 8; i++) { m16 |= ((my >> i) & 1u) << (7 - i); m16 |= ((mx >> i) & 1u) << (15 - i); }
 #endif
+  // ... and of the text bytes that are no letters (a sequence's terminator, the padding in front of the first sequence): no
+  // substitute exists there (only letters are tried), the chain ends in front of such a byte whatever is left to spend.  Rare:
+  // the mask is made only when there is one (text bytes are codes 0 .. 20, a zero byte is the one that borrows into its bit 7)
+  if ((((tx.x - 0x0101010101010101ull) | (tx.y - 0x0101010101010101ull)) & 0x8080808080808080ull) != 0ull) {
+    const uint32_t zx = ~diff_bits(tx.x) & 0xffu, zy = ~diff_bits(tx.y) & 0xffu;
+#if defined(__HIP_DEVICE_COMPILE__)
+    z16 = (__brev(zy) >> 24) | (__brev(zx) >> 24) << 8;
+#else
+    for (int i = 0; i < 8; i++) { z16 |= ((zy >> i) & 1u) << (7 - i); z16 |= ((zx >> i) & 1u) << (15 - i); }
+#endif
+  }
   if (a < 16) m16 |= 0xffffu << a;                          // in front of the fragment's start nothing matches and nothing is substituted
   // the substitutions that are left take the first differences; the chain ends in front of the next one
   uint32_t m = m16;
   for (uint32_t q = nmm; q < p.mismatches && m; q++) m &= m - 1u;
+  m |= z16;                                                 // (a byte that is no letter differs from every letter: it was one of them)
   if (m == 0) return false;                                 // fewer differences than that within sixteen letters: it may go on
   int e = 0;
   while (!((m >> e) & 1u)) e++;
@@ -5175,6 +5188,7 @@ KJ_HD void greedy_lane2(const DevIndex &ix, const ConstTables &ct, const Params 
             const P nrows = rb - ra;
             if (nrows <= (P)kChainRows && ix.sa_full && ix.text && (m_ql + 1u < p.m || sc0 < thr)) {
               bool hopeless = true;
+              KJ_HISTO(13, (int)pz - wq); KJ_HISTO(14, wq > 0 ? 1 : 0);       // (the window the rule is asked with: a, and whether it starts with the fragment)
               for (P q = ra; q < rb && hopeless; q++) {
                 // (the text position of the variant's match: one letter in front of its parent's when that had one row - that
                 //  row's position came with the rank lines -, else the entry of the row)

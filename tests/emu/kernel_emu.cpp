@@ -126,6 +126,35 @@ uint64_t emu_rank(void *h, uint32_t c, uint64_t k) {
 }
 uint32_t emu_symbol(void *h, uint64_t k) { DevIndex d = ((EmuIndex *)h)->packed.host_view(); return symbol_at(d, k); }
 
+// the library's BLOSUM62 (host_tables.cpp: build_const_tables) for two codes 1 .. 20 of the index alphabet, as the lanes read it:
+// the substitution score table b62_idx, and the diagonal table diag_idx where c == d and diag != 0; -128 outside
+int emu_b62(void *h, uint32_t c, uint32_t d, int diag) {
+  const ConstTables &ct = ((EmuIndex *)h)->ct;
+  if (c < 1 || c > 20 || d < 1 || d > 20) return -128;
+  if (diag) return c == d ? (int)ct.diag_idx[c] : -128;
+  return (int)ct.b62_idx[ct.idx_to_aa[c]][d - 1];
+}
+
+// greedy_lane2's pruning rule by itself (the host's compilation of kj_chain_hopeless; the device's: kaiju_gpu_chain_hopeless_check,
+// the same cases, the same bounds): out[i] = 1 hopeless, 0 not; 0 or KAIJU_GPU_ERR_ARG
+int emu_chain_hopeless(const kaiju_gpu_chain_case *cases, uint32_t n, uint8_t *out) {
+  static_assert(KAIJU_GPU_CHAIN_WIN == kGWinStride * 4, "a case holds a window row of the Greedy lane");
+  for (uint32_t r = 0; r < n; r++) {
+    const kaiju_gpu_chain_case &c = cases[r];
+    if (c.wq < 0 || c.pz < 0 || c.pz > 0xffff || c.j < c.pz || c.j > 0xffff || c.pz - c.wq >= kWin || c.mismatches > (uint32_t)kMaxMismatch ||
+        c.nmm > c.mismatches)
+      return KAIJU_GPU_ERR_ARG;
+    alignas(16) uint32_t row[kGWinStride];
+    memcpy(row, c.win, sizeof row);
+    Params p{};
+    p.m = c.m; p.mismatches = c.mismatches;
+    u128 tx;
+    memcpy(&tx.x, c.tx, 8); memcpy(&tx.y, c.tx + 8, 8);
+    out[r] = kj_chain_hopeless(p, reinterpret_cast<const uint8_t *>(row), c.wq, c.pz, c.j, tx, c.nmm, c.sc0, c.thr) ? 1 : 0;
+  }
+  return 0;
+}
+
 // SEG on an ASCII peptide (letters of the 20 amino acids)
 // the SEG code's cooperation object of the emulation: one lane, with the prefix-count scratch of s_Trim (the device's k_seg
 // has it in LDS) unless KAIJU_EMU_NO_SEG_PREFIX is set (every sub-window then counts its own letters: the two must agree)

@@ -65,6 +65,18 @@ def test_seg_regions_entry_needs_a_device():
     assert rc == (-4 if api.device_count() == 0 else -1)                      # KAIJU_GPU_ERR_NO_DEVICE / KAIJU_GPU_ERR_ARG
 
 
+def test_chain_hopeless_entry_needs_a_device():
+    """kaiju_gpu_chain_hopeless_check (diagnostics: the Greedy lane's pruning rule by itself) runs the device's compilation of
+    the rule only: without a device it says so, with one a call with cases and no buffers is a bad argument; the record is the
+    header's"""
+    L = api.lib()
+    L.kaiju_gpu_chain_hopeless_check.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    assert L.kaiju_gpu_chain_hopeless_check(0, None, 3, None) == (-4 if api.device_count() == 0 else -1)
+    src = open(HEADER).read()
+    assert api.CHAIN_CASE_DTYPE.itemsize == 116 and f"#define KAIJU_GPU_CHAIN_WIN {api.CHAIN_WIN}\n" in src
+    assert [n for n in api.CHAIN_CASE_DTYPE.names] == ["win", "tx", "wq", "pz", "j", "sc0", "thr", "nmm", "m", "mismatches"]
+
+
 def test_index_read_back_entries_need_a_device():
     """kaiju_gpu_index_get_layout / kaiju_gpu_index_read_array (diagnostics: the arrays of an index as they lie in HBM) hand out
     device memory only: without a device they say so, with one a call without an index is a bad argument"""
