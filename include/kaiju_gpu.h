@@ -774,6 +774,14 @@ int kaiju_gpu_krona_pass_ms(kaiju_gpu_krona *k, float *ms, uint32_t n);
 typedef struct kaiju_gpu_accmap kaiju_gpu_accmap;
 int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, uint32_t key_col,
                             uint32_t taxon_col, uint64_t initial_slots, kaiju_gpu_accmap **out);
+/* The same with a rule set in place of the columns.  KAIJU_GPU_CONVERT_RULES_NR: what kaiju_gpu_accmap_create (1, 2) makes.
+   KAIJU_GPU_CONVERT_RULES_REFSEQ: the map of kaiju-convertRefSeq.cpp:145-195 - two columns accession.version '\t' taxon, only
+   lines that begin with "WP_", taxon 0 inserts nothing, and an accession whose taxon came through merged.dmp loses its last
+   byte, as in the tool (kj_convert.h, "kaiju-convertRefSeq").  kaiju_gpu_accmap_add_keys, _lookup, _info and the growth are
+   the same for both.  Any other value: KAIJU_GPU_ERR_ARG. */
+enum { KAIJU_GPU_CONVERT_RULES_NR = 0, KAIJU_GPU_CONVERT_RULES_REFSEQ = 1 };
+int kaiju_gpu_accmap_create_rules(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, int rules,
+                                  uint64_t initial_slots, kaiju_gpu_accmap **out);
 void kaiju_gpu_accmap_free(kaiju_gpu_accmap *m);
 /* A block of the map file, cut behind a line end (the last block need not end in one); is_first_block: its first line is the
    file's header line and is skipped.  Blocks below 2^32 - 16 bytes.  The call blocks.  The _device form takes a 16-byte aligned
@@ -811,6 +819,14 @@ int kaiju_gpu_accmap_pass_ms(kaiju_gpu_accmap *m, float *ms, uint32_t n);
 typedef struct kaiju_gpu_converter kaiju_gpu_converter;
 int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
                                const kaiju_gpu_accmap *excluded, int add_acc, kaiju_gpu_converter **out);
+/* The same with a rule set.  KAIJU_GPU_CONVERT_RULES_NR: kaiju_gpu_converter_create without an excluded map.
+   KAIJU_GPU_CONVERT_RULES_REFSEQ: what kaiju-convertRefSeq.cpp:205-265 writes - the one accession of a header is [1, first
+   space), a header without a space is dropped, '\x01' is a byte like any other, the record's taxon is the entry's (no LCA, no
+   excluded set); the output is built as above.  `map` must have been made with the same rule set (KAIJU_GPU_ERR_ARG).  In
+   kaiju_gpu_convert_info n_entries counts the headers that have a space, n_hits those found; dropped_excluded and
+   dropped_no_lca stay 0. */
+int kaiju_gpu_converter_create_rules(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
+                                     int rules, int add_acc, kaiju_gpu_converter **out);
 void kaiju_gpu_converter_free(kaiju_gpu_converter *c);
 typedef struct kaiju_gpu_convert_info {
   uint64_t text_bytes;             /* of the whole output, also when it overflowed                                         */

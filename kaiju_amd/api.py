@@ -280,6 +280,9 @@ def lib():
         L.kaiju_gpu_convert_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.kaiju_gpu_convert_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
         L.kaiju_gpu_convert_pass_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    if hasattr(L, "kaiju_gpu_accmap_create_rules"):           # (likewise)
+        L.kaiju_gpu_accmap_create_rules.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]
+        L.kaiju_gpu_converter_create_rules.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "kaiju_gpu_gbk_create"):                    # (likewise)
         L.kaiju_gpu_gbk_create.argtypes = [C.c_int, C.c_void_p]
         L.kaiju_gpu_gbk_free.argtypes = [C.c_void_p]
@@ -817,19 +820,34 @@ class Krona:
             pass
 
 
-class AccMap:
-    """The accession -> taxon map of kaiju-convertNR on the device (kaiju_gpu_accmap_create).  dtax: the tree whose nodes decide
-    which lines insert (None: a map for add_keys only, the excluded accessions); merged: (old id, new id) pairs of merged.dmp in
-    file order."""
+CONVERT_RULES = {"nr": 0, "refseq": 1}                        # KAIJU_GPU_CONVERT_RULES_NR, _REFSEQ
 
-    def __init__(self, dtax=None, merged=(), device=0, initial_slots=0, key_col=1, taxon_col=2):
+
+def _rules(rules):
+    if rules not in CONVERT_RULES:
+        raise KaijuGpuError("rules is 'nr' or 'refseq', not %r" % (rules,))
+    if rules != "nr" and not hasattr(lib(), "kaiju_gpu_accmap_create_rules"):
+        raise KaijuGpuError("this library has no rule sets (kaiju_gpu_accmap_create_rules)")
+    return CONVERT_RULES[rules]
+
+
+class AccMap:
+    """The accession -> taxon map of kaiju-convertNR (rules="nr": kaiju_gpu_accmap_create) or of kaiju-convertRefSeq
+    (rules="refseq": kaiju_gpu_accmap_create_rules) on the device.  dtax: the tree whose nodes decide which lines insert (None: a
+    map for add_keys only, the excluded accessions); merged: (old id, new id) pairs of merged.dmp in file order."""
+
+    def __init__(self, dtax=None, merged=(), device=0, initial_slots=0, key_col=1, taxon_col=2, rules="nr"):
         if not hasattr(lib(), "kaiju_gpu_accmap_create"):
             raise KaijuGpuError("this library was linked without accmap.hip")
         self._tax = dtax                                      # (the tree must outlive the map)
         self._h = C.c_void_p()
+        self.rules = rules
         pairs = np.array([x for p in merged for x in p], dtype=np.uint64)
-        _check(lib().kaiju_gpu_accmap_create(dtax._h if dtax is not None else None, device, pairs.ctypes.data if len(pairs) else None, len(pairs) // 2,
-                                             key_col, taxon_col, initial_slots, C.byref(self._h)))
+        tax, p = dtax._h if dtax is not None else None, pairs.ctypes.data if len(pairs) else None
+        if _rules(rules):
+            _check(lib().kaiju_gpu_accmap_create_rules(tax, device, p, len(pairs) // 2, CONVERT_RULES[rules], initial_slots, C.byref(self._h)))
+        else:
+            _check(lib().kaiju_gpu_accmap_create(tax, device, p, len(pairs) // 2, key_col, taxon_col, initial_slots, C.byref(self._h)))
 
     def add_text(self, text: bytes, first_block=True):
         """a block of the map file, cut behind a line end; first_block: its first line is the file's header line"""
@@ -881,18 +899,25 @@ class AccMap:
 
 class Converter:
     """kaiju-convertNR on blocks of nr-style text (kaiju_gpu_converter_create): per kept record '>' [accession '_'] taxon '\n'
-    letters '\n'.  include: the ids of -l that are nodes (None: 2, 2157, 10239); excluded: an AccMap built with add_keys."""
+    letters '\n'.  include: the ids of -l that are nodes (None: 2, 2157, 10239); excluded: an AccMap built with add_keys.
+    rules="refseq": kaiju-convertRefSeq (kaiju_gpu_converter_create_rules) - one accession per header, no LCA, no excluded
+    map; amap must have been made with the same rules."""
 
-    def __init__(self, dtax, amap: AccMap, excluded: AccMap = None, include=None, add_acc=False):
+    def __init__(self, dtax, amap: AccMap, excluded: AccMap = None, include=None, add_acc=False, rules="nr"):
         if not hasattr(lib(), "kaiju_gpu_converter_create"):
             raise KaijuGpuError("this library was linked without convert.hip")
+        if _rules(rules) and excluded is not None:
+            raise KaijuGpuError("the rules of kaiju-convertRefSeq have no excluded accessions")
         self._keep = (dtax, amap, excluded)                   # (they must outlive the converter)
         self._h = C.c_void_p()
         ids = np.array(list(include) if include is not None else [], dtype=np.uint64)
         if include is not None and not len(ids):
             ids = np.array([2 ** 64 - 1], dtype=np.uint64)   # an empty list keeps nothing: an id that is never a node
-        _check(lib().kaiju_gpu_converter_create(dtax._h, ids.ctypes.data if include is not None else None, len(ids) if include is not None else 0, amap._h,
-                                                excluded._h if excluded is not None else None, 1 if add_acc else 0, C.byref(self._h)))
+        p, n = (ids.ctypes.data, len(ids)) if include is not None else (None, 0)
+        if _rules(rules):
+            _check(lib().kaiju_gpu_converter_create_rules(dtax._h, p, n, amap._h, CONVERT_RULES[rules], 1 if add_acc else 0, C.byref(self._h)))
+        else:
+            _check(lib().kaiju_gpu_converter_create(dtax._h, p, n, amap._h, excluded._h if excluded is not None else None, 1 if add_acc else 0, C.byref(self._h)))
 
     def convert(self, text: bytes, out_cap=None):
         """Returns (bytes, info): the records of a block that starts at a header line (or is the start of the file) and a

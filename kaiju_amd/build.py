@@ -77,6 +77,7 @@ def build(force=False, verbose=False):
     build_table_cli(force=force, verbose=verbose)
     build_krona_cli(force=force, verbose=verbose)
     build_convert_cli(force=force, verbose=verbose)
+    build_refseq_cli(force=force, verbose=verbose)
     build_gbk_cli(force=force, verbose=verbose)
     return LIB
 
@@ -170,7 +171,7 @@ def build_krona_cli(force=False, verbose=False):
     return KRONA_CLI
 
 
-CONVERT_SRC = [os.path.join(CSRC, "host", f) for f in ("convert_main.cpp", "convert_blocks.h", "pargz.h")]
+CONVERT_SRC = [os.path.join(CSRC, "host", f) for f in ("convert_main.cpp", "convert_blocks.h", "refseq_options.h", "pargz.h")]
 CONVERT_CLI = os.path.join(HERE, "bin", "kaiju-convertNR")
 
 
@@ -184,6 +185,21 @@ def build_convert_cli(force=False, verbose=False):
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
     return CONVERT_CLI
+
+
+REFSEQ_CLI = os.path.join(HERE, "bin", "kaiju-convertRefSeq")
+
+
+def build_refseq_cli(force=False, verbose=False):
+    """the drop-in `kaiju-convertRefSeq` command: the source of `kaiju-convertNR` compiled for the other rule set"""
+    if not force and os.path.exists(REFSEQ_CLI) and os.path.getmtime(REFSEQ_CLI) >= max([os.path.getmtime(LIB)] + [os.path.getmtime(s) for s in CONVERT_SRC]):
+        return REFSEQ_CLI
+    os.makedirs(os.path.dirname(REFSEQ_CLI), exist_ok=True)
+    cmd = ["g++", "-O2", "-std=c++17", "-DKAIJU_CONVERT_REFSEQ", "-o", REFSEQ_CLI, CONVERT_SRC[0], "-L" + HERE, "-lkaiju_gpu", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return REFSEQ_CLI
 
 
 GBK_SRC = [os.path.join(CSRC, "host", f) for f in ("gbk_main.cpp", "gbk_blocks.h", "pargz.h")]

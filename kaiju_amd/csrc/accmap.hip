@@ -1,8 +1,9 @@
-// accmap.hip — the accession -> taxon map of kaiju-convertNR on the device (gfx950, wave64): the entry points
-// kaiju_gpu_accmap_* of include/kaiju_gpu.h.  The rules and the layout: kj_convert.h.
+// accmap.hip — the accession -> taxon map of kaiju-convertNR and kaiju-convertRefSeq on the device (gfx950, wave64): the entry
+// points kaiju_gpu_accmap_* of include/kaiju_gpu.h.  The rules of either tool and the layout: kj_convert.h.
 //
 // per block   k_tl_*         the lines of the block                                                    (kj_textlines.h)
-//             k_am_parse     one lane per line: key span, taxon, node / merged decision; what the block needs of the arena
+//             k_am_parse     one lane per line: key span, taxon, node / merged decision by the map's rule set (parse_map_line or
+//                            refseq_map_line); what the block needs of the arena
 //             (the host reads the two counts, grows the arena by reallocation and the slots by k_am_rehash)
 //             k_am_insert    one lane per line that inserts: probe; an empty slot takes a new entry by compare-and-swap, an
 //                            equal key takes the minimum of the line numbers
@@ -47,7 +48,7 @@ struct AmJob {
   uint64_t *slots, mask;
   uint8_t *arena;
   uint64_t ord_base, value;
-  int first_block, keys_only;
+  int first_block, keys_only, rules;
 };
 
 void carve(kjl::Carver &c, AmJob &J) {
@@ -73,9 +74,14 @@ __global__ __launch_bounds__(kAmBlock) void k_am_parse(AmJob J, Tree T, Merged G
     const uint64_t a = J.t.line_start[i], e = (uint64_t)J.t.line_start[i + 1] - 1;
     if (a >= e || (J.first_block && i == 0)) continue;
     lines++;
-    MapLine L = parse_map_line(J.t.text, a, e, J.keys_only != 0, J.value);
+    MapLine L;
     uint32_t slot;
-    if (!L.valid || (!J.keys_only && !resolve_taxon(T, G, &L.taxon, &slot))) { none++; continue; }
+    if (J.rules == kRulesRefSeq && !J.keys_only) L = refseq_map_line(J.t.text, a, e, T, G);
+    else {
+      L = parse_map_line(J.t.text, a, e, J.keys_only != 0, J.value);
+      if (L.valid && !J.keys_only) L.valid = resolve_taxon(T, G, &L.taxon, &slot);
+    }
+    if (!L.valid) { none++; continue; }
     J.key_pos[i] = (uint32_t)L.key;
     J.key_len[i] = (uint32_t)(L.key_end - L.key);
     J.taxon[i] = L.taxon;
@@ -199,6 +205,7 @@ struct kaiju_gpu_accmap {
   AmHdr *hdr = nullptr;                // device
   AmHdr host{};                        // what the last call left
   uint64_t ord_base = 0, rehashes = 0;
+  int rules = kRulesNr;
   kjl::Scratch scratch, text, out;
   hipStream_t stream = nullptr;
   bool timed = false;
@@ -269,7 +276,7 @@ int add(kaiju_gpu_accmap *m, const void *d_text, uint64_t bytes, int first_block
   if (int rc = m->scratch.reserve(measure.at, 256, "hipMalloc of the accession map's scratch", &err)) return fail(rc, err);
   kjl::Carver c{static_cast<uint8_t *>(m->scratch.p)};
   carve(c, J);
-  J.hdr = m->hdr; J.ord_base = m->ord_base; J.value = value; J.first_block = first_block ? 1 : 0; J.keys_only = keys_only;
+  J.hdr = m->hdr; J.ord_base = m->ord_base; J.value = value; J.first_block = first_block ? 1 : 0; J.keys_only = keys_only; J.rules = m->rules;
   const hipStream_t s = m->stream;
   const dim3 blk(kAmBlock), grid = grid_for(bytes / 4);
   int mark = 0;
@@ -315,13 +322,16 @@ kjc::Map kj_accmap_view(const kaiju_gpu_accmap *m, const kaiju_gpu_taxonomy **ta
   if (device) *device = m->device;
   return Map{m->slots, m->n_slots - 1, m->arena};
 }
+int kj_accmap_rules(const kaiju_gpu_accmap *m) { return m->rules; }
 
-extern "C" int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, uint32_t key_col,
-                                       uint32_t taxon_col, uint64_t initial_slots, kaiju_gpu_accmap **out) {
+static_assert(kRulesNr == KAIJU_GPU_CONVERT_RULES_NR && kRulesRefSeq == KAIJU_GPU_CONVERT_RULES_REFSEQ, "the rule sets of kj_convert.h are those of kaiju_gpu.h");
+
+extern "C" int kaiju_gpu_accmap_create_rules(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, int rules,
+                                             uint64_t initial_slots, kaiju_gpu_accmap **out) {
   return guarded([&]() -> int {
     if (!out || (!merged_pairs && n_merged)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (key_col != 1 || taxon_col != 2) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the key is column 1 and the taxon column 2 (prot.accession2taxid); other columns are not built yet");
+    if (rules != kRulesNr && rules != kRulesRefSeq) return fail(KAIJU_GPU_ERR_ARG, "the rule set is KAIJU_GPU_CONVERT_RULES_NR or KAIJU_GPU_CONVERT_RULES_REFSEQ");
     if (tax && tax->device != device_id) return fail(KAIJU_GPU_ERR_ARG, "the tree lives on another device");
     if (n_merged > 0xfffffff0ull) return fail(KAIJU_GPU_ERR_ARG, "too many merged pairs");
     if (initial_slots > (1ull << 40)) return fail(KAIJU_GPU_ERR_ARG, "initial_slots above 2^40");
@@ -339,6 +349,7 @@ extern "C" int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device
     struct Guard { kaiju_gpu_accmap *p; ~Guard() { kaiju_gpu_accmap_free(p); } } guard{m};
     m->device = device_id;
     m->tax = tax;
+    m->rules = rules;
     if (tax) m->tree = Tree{tax->dev.key, tax->dev.parent_slot, tax->dev.depth, tax->dev.cap_mask};
     if (hipSetDevice(m->device) != hipSuccess || hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return fail(KAIJU_GPU_ERR_HIP, "hipStreamCreate of the accession map"); }
     const char *e = getenv("KAIJU_GPU_CONVERT_TIMES");
@@ -370,6 +381,18 @@ extern "C" int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device
     *out = m;
     return KAIJU_GPU_OK;
   });
+}
+
+extern "C" int kaiju_gpu_accmap_create(const kaiju_gpu_taxonomy *tax, int device_id, const uint64_t *merged_pairs, uint64_t n_merged, uint32_t key_col,
+                                       uint32_t taxon_col, uint64_t initial_slots, kaiju_gpu_accmap **out) {
+  const int rc = guarded([&]() -> int {
+    if (!out || (!merged_pairs && n_merged)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (key_col != 1 || taxon_col != 2) return fail(KAIJU_GPU_ERR_UNSUPPORTED, "the key is column 1 and the taxon column 2 (prot.accession2taxid); other columns are not built yet");
+    return KAIJU_GPU_OK;
+  });
+  if (rc != KAIJU_GPU_OK) return rc;
+  return kaiju_gpu_accmap_create_rules(tax, device_id, merged_pairs, n_merged, KAIJU_GPU_CONVERT_RULES_NR, initial_slots, out);
 }
 
 extern "C" void kaiju_gpu_accmap_free(kaiju_gpu_accmap *m) {

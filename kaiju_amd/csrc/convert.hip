@@ -1,5 +1,5 @@
-// convert.hip — kaiju-convertNR on a block of nr-style text (gfx950, wave64): the passes of kj_convert.h as kernels, and the
-// entry points kaiju_gpu_converter_* / kaiju_gpu_convert_* of include/kaiju_gpu.h.  The host never learns a count while the
+// convert.hip — kaiju-convertNR and kaiju-convertRefSeq on a block of FASTA text (gfx950, wave64): the passes of kj_convert.h as
+// kernels, and the entry points kaiju_gpu_converter_* / kaiju_gpu_convert_* of include/kaiju_gpu.h.  The host never learns a count while the
 // passes are queued: every kernel behind the first sizes itself from counts in device memory.
 //
 // at create   k_cv_listed / k_cv_keep   per slot of the tree: is it on the include list; does the include walk from it keep
@@ -10,6 +10,8 @@
 //             k_cv_records     one lane per line: rec_line[] and the start values of a record's reduction
 //             k_cv_entries     one lane per 16 bytes of text: the entries that start in them, the lookups in both maps, the
 //                              record's reduction with atomics (LCA by compare-and-swap, excluded, first accession)
+//             k_cv_first       in its place under the RefSeq rules: one lane per record, the header read in 16-byte chunks up
+//                              to its first space, one lookup, plain stores
 //             k_cv_decide      one lane per record: the taxon or the reason it is dropped
 //             k_cv_len         one lane per line: the bytes it gives to the output
 //             kjl::k_scan_* <CvLines>   line_off[]
@@ -174,6 +176,27 @@ __global__ __launch_bounds__(kCvBlock) void k_cv_entries(CvJob J, Tree T, Map M,
   }
 }
 
+// The RefSeq rules: one accession at the front of each header.  One lane per record and no atomics on the records: the lane
+// owns rec_lca, rec_flags and rec_first of its record.  What a lane waits for is a chain of dependent loads (rec_line,
+// line_start, the header's chunks, the slot of the map, the entry, the slot of the tree) and nothing else: no LDS, few
+// registers, so blocks of 256 lanes fill a CU with its 32 wavefronts and the chains of that many records overlap.
+__global__ __launch_bounds__(kCvBlock) void k_cv_first(CvJob J, Tree T, Map M) {
+  const uint32_t n = *J.t.n_lines, n_rec = (uint32_t)J.hdr_pos[n];
+  cv_u64 entries = 0, hits = 0;
+  for (uint32_t r = blockIdx.x * kCvBlock + threadIdx.x; r < n_rec; r += gridDim.x * kCvBlock) {
+    const uint32_t i = J.rec_line[r];
+    const First F = first_entry(J.t.text, J.t.line_start[i], (uint64_t)J.t.line_start[i + 1] - 1, M, T);
+    J.rec_lca[r] = F.slot; J.rec_first[r] = F.first; J.rec_flags[r] = 0;
+    entries += F.entry; hits += F.hit;
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { entries += __shfl_xor(entries, d, 64); hits += __shfl_xor(hits, d, 64); }
+  if ((threadIdx.x & 63) == 0 && entries) {
+    atomicAdd(reinterpret_cast<cv_u64 *>(&J.hdr->n_entries), entries);
+    atomicAdd(reinterpret_cast<cv_u64 *>(&J.hdr->n_hits), hits);
+  }
+}
+
 __global__ __launch_bounds__(kCvBlock) void k_cv_decide(CvJob J, Tree T, const uint8_t *keep) {
   const uint32_t n = *J.t.n_lines, n_rec = (uint32_t)J.hdr_pos[n];
   cv_u64 cnt[5] = {0, 0, 0, 0, 0};                            // kept, excluded, no taxon, not included, no lca
@@ -237,7 +260,7 @@ struct kaiju_gpu_converter {
   int device = -1;
   const kaiju_gpu_taxonomy *tax = nullptr;
   const kaiju_gpu_accmap *map = nullptr, *excluded = nullptr;
-  int add_acc = 0;
+  int add_acc = 0, rules = kRulesNr;
   Tree tree{};
   uint8_t *listed = nullptr, *keep = nullptr;
   uint64_t *d_ids = nullptr;
@@ -286,7 +309,8 @@ int launch(kaiju_gpu_converter *k, hipStream_t s, const void *d_text, uint64_t b
   kjl::launch_offsets(s, sgrid, count, static_cast<const uint8_t *>(J.is_header), J.blk, J.blk_base, J.hdr_pos);
   hipLaunchKernelGGL(k_cv_records, lgrid, blk, 0, s, J);
   passed();
-  hipLaunchKernelGGL(k_cv_entries, cgrid, blk, 0, s, J, k->tree, M, X);
+  if (k->rules == kRulesRefSeq) hipLaunchKernelGGL(k_cv_first, lgrid, blk, 0, s, J, k->tree, M);
+  else hipLaunchKernelGGL(k_cv_entries, cgrid, blk, 0, s, J, k->tree, M, X);
   passed();
   hipLaunchKernelGGL(k_cv_decide, lgrid, blk, 0, s, J, k->tree, static_cast<const uint8_t *>(k->keep));
   passed();
@@ -302,13 +326,13 @@ int launch(kaiju_gpu_converter *k, hipStream_t s, const void *d_text, uint64_t b
   return KAIJU_GPU_OK;
 }
 
-}  // namespace
-
-extern "C" int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
-                                          const kaiju_gpu_accmap *excluded, int add_acc, kaiju_gpu_converter **out) {
+int create(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map, const kaiju_gpu_accmap *excluded, int rules,
+           int add_acc, kaiju_gpu_converter **out) {
   return guarded([&]() -> int {
     if (!tax || !map || !out || (!include_ids && n_include)) return fail(KAIJU_GPU_ERR_ARG, "NULL argument");
     *out = nullptr;
+    if (rules != kRulesNr && rules != kRulesRefSeq) return fail(KAIJU_GPU_ERR_ARG, "the rule set is KAIJU_GPU_CONVERT_RULES_NR or KAIJU_GPU_CONVERT_RULES_REFSEQ");
+    if (kj_accmap_rules(map) != rules) return fail(KAIJU_GPU_ERR_ARG, "the accession map was made for the other rule set");
     const kaiju_gpu_taxonomy *map_tax = nullptr;
     int map_dev = -1, ex_dev = -1;
     (void)kj_accmap_view(map, &map_tax, &map_dev);
@@ -320,7 +344,7 @@ extern "C" int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const u
 
     kaiju_gpu_converter *k = new kaiju_gpu_converter();
     struct Guard { kaiju_gpu_converter *p; ~Guard() { kaiju_gpu_converter_free(p); } } guard{k};
-    k->device = tax->device; k->tax = tax; k->map = map; k->excluded = excluded; k->add_acc = add_acc ? 1 : 0;
+    k->device = tax->device; k->tax = tax; k->map = map; k->excluded = excluded; k->add_acc = add_acc ? 1 : 0; k->rules = rules;
     k->tree = Tree{tax->dev.key, tax->dev.parent_slot, tax->dev.depth, tax->dev.cap_mask};
     if (hipSetDevice(k->device) != hipSuccess || hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&k->done, hipEventDisableTiming) != hipSuccess || hipHostMalloc(&k->h_info, sizeof(kaiju_gpu_convert_info) + 8, hipHostMallocDefault) != hipSuccess) {
@@ -349,6 +373,18 @@ extern "C" int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const u
     *out = k;
     return KAIJU_GPU_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int kaiju_gpu_converter_create(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
+                                          const kaiju_gpu_accmap *excluded, int add_acc, kaiju_gpu_converter **out) {
+  return create(tax, include_ids, n_include, map, excluded, kRulesNr, add_acc, out);
+}
+
+extern "C" int kaiju_gpu_converter_create_rules(const kaiju_gpu_taxonomy *tax, const uint64_t *include_ids, uint32_t n_include, const kaiju_gpu_accmap *map,
+                                                int rules, int add_acc, kaiju_gpu_converter **out) {
+  return create(tax, include_ids, n_include, map, nullptr, rules, add_acc, out);
 }
 
 extern "C" void kaiju_gpu_converter_free(kaiju_gpu_converter *k) {

@@ -12,6 +12,11 @@
 //                          the map file) that is larger is an error that names its size
 // Deliberately different (also in the usage text): the chatter of -v / -d on stderr is not reproduced, -v prints a summary; and
 // on a taxonomy that is no single tree a record whose taxa have no common ancestor is dropped and counted where the tool hangs.
+//
+// Compiled with -DKAIJU_CONVERT_REFSEQ this is kaiju-convertRefSeq, the same program under the other rule set of kj_convert.h:
+//   kaiju-convertRefSeq -t nodes.dmp -m merged.dmp -g prot.accession2taxid.FULL -o out.faa [-a] [-l list] [-v] [-d]   < text
+// The tool reads standard input only and has no excluded accessions: -i, -e and -r end in the usage (refseq_options.h).  Map
+// and converters are made with KAIJU_GPU_CONVERT_RULES_REFSEQ; files, blocks, streams and the order of the output are the same.
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -28,10 +33,37 @@
 #include "../../../include/kaiju_gpu.h"
 #include "convert_blocks.h"
 #include "pargz.h"
+#include "refseq_options.h"
 
 namespace {
 
+#ifdef KAIJU_CONVERT_REFSEQ
+constexpr bool kRefSeq = true;
+#else
+constexpr bool kRefSeq = false;
+#endif
+constexpr int kRules = kRefSeq ? KAIJU_GPU_CONVERT_RULES_REFSEQ : KAIJU_GPU_CONVERT_RULES_NR;
+
+void usage_refseq(const char *prog) {
+  fprintf(stderr,
+          "Usage:\n   %s -t nodes.dmp -m merged.dmp -g prot.accession2taxid -o out.faa   < protein FASTA\n"
+          "Mandatory arguments:\n"
+          "   -t FILENAME   Name of nodes.dmp file.\n"
+          "   -m FILENAME   Name of merged.dmp file.\n"
+          "   -g FILENAME   Name of prot.accession2taxid.FULL file (may be gzip-compressed).\n"
+          "   -o FILENAME   Name of output file.\n"
+          "Optional arguments:\n"
+          "   -a            Prefix taxon ID with the accession number.\n"
+          "   -l FILENAME   Name of file with taxon IDs. Only records having one of these IDs as ancestor in the taxonomy will be used.\n"
+          "   -v            Print a summary. (The per-accession messages of the reference tool are not reproduced.)\n"
+          "   -d            Accepted; the debug messages of the reference tool are not reproduced.\n"
+          "The text is read from standard input.\n",
+          prog);
+  exit(EXIT_FAILURE);
+}
+
 void usage(const char *prog) {
+  if (kRefSeq) usage_refseq(prog);
   fprintf(stderr,
           "Usage:\n   %s -t nodes.dmp -m merged.dmp -g prot.accession2taxid -o out.faa [-i nr]\n"
           "Mandatory arguments:\n"
@@ -112,7 +144,7 @@ struct Slot {
 }  // namespace
 
 int main(int argc, char **argv) {
-  const kjcb::Options opt = kjcb::parse_options(argc, argv);
+  const kjcb::Options opt = kRefSeq ? kjrs::parse_options(argc, argv) : kjcb::parse_options(argc, argv);
   if (opt.help || opt.bad_option) usage(argv[0]);
   if (!opt.error.empty()) { error(opt.error); usage(argv[0]); }
 
@@ -143,7 +175,7 @@ int main(int argc, char **argv) {
   kaiju_gpu_taxonomy *dtax = nullptr;
   if (kaiju_gpu_taxonomy_upload(tax, device, &dtax) != KAIJU_GPU_OK) die(kaiju_gpu_last_error());
   kaiju_gpu_accmap *map = nullptr, *excluded = nullptr;
-  if (kaiju_gpu_accmap_create(dtax, device, pairs.data(), pairs.size() / 2, 1, 2, 0, &map) != KAIJU_GPU_OK) die(kaiju_gpu_last_error());
+  if (kaiju_gpu_accmap_create_rules(dtax, device, pairs.data(), pairs.size() / 2, kRules, 0, &map) != KAIJU_GPU_OK) die(kaiju_gpu_last_error());
   {
     MaybeGz src(opt.map);
     kjcb::Cutter cutter([&](char *dst, size_t n) { return src.read(dst, n); }, block, kjcb::Cutter::kLines);
@@ -173,9 +205,12 @@ int main(int argc, char **argv) {
   if (!out) die("Could not open file " + opt.out + " for writing.");
 
   Slot slot[2];
-  for (Slot &s : slot)
-    if (kaiju_gpu_converter_create(dtax, include.empty() ? nullptr : include.data(), (uint32_t)include.size(), map, excluded, opt.add_acc ? 1 : 0, &s.cv) != KAIJU_GPU_OK)
-      die(kaiju_gpu_last_error());
+  for (Slot &s : slot) {
+    const uint64_t *ids = include.empty() ? nullptr : include.data();
+    const int rc = kRefSeq ? kaiju_gpu_converter_create_rules(dtax, ids, (uint32_t)include.size(), map, kRules, opt.add_acc ? 1 : 0, &s.cv)
+                           : kaiju_gpu_converter_create(dtax, ids, (uint32_t)include.size(), map, excluded, opt.add_acc ? 1 : 0, &s.cv);
+    if (rc != KAIJU_GPU_OK) die(kaiju_gpu_last_error());
+  }
 
   kaiju_gpu_convert_info sum{};
   uint64_t written = 0;

@@ -1,5 +1,6 @@
 // kj_convert.h — kaiju-convertNR on blocks of text: the per-lane logic, for the device (accmap.hip, convert.hip) and for the
-// host (tests/emu/convert_emu.cpp drives the same functions pass by pass).
+// host (tests/emu/convert_emu.cpp drives the same functions pass by pass).  kaiju-convertRefSeq is a second rule set over the
+// same map and the same passes: its rules stand with its code below ("kaiju-convertRefSeq"; tests/emu/refseq_emu.cpp).
 //
 // The rules are those of kaiju-convertNR.cpp:145-306 and util.cpp:79-121, :194-263 of the reference (getline, find, substr,
 // strtoul, unordered_map::emplace, lca_from_ids), observed on the unmodified tool (tests/golden/convert/):
@@ -163,9 +164,10 @@ KJF_HD MapLine parse_map_line(const uint8_t *text, uint64_t a, uint64_t e, bool 
   return L;
 }
 struct Merged { const uint64_t *from, *to; uint32_t n; };    // sorted by `from`, one pair per id
-// the node a taxon of the map file stands for: *slot, or false
-KJF_HD bool resolve_taxon(const Tree &T, const Merged &G, uint64_t *taxon, uint32_t *slot) {
+// the node a taxon of the map file stands for: *slot, or false.  *via_merged: the taxon itself is no node, `merged` gave the node
+KJF_HD bool resolve_taxon(const Tree &T, const Merged &G, uint64_t *taxon, uint32_t *slot, bool *via_merged = nullptr) {
   uint32_t s = kjm::find_slot(T, *taxon);
+  if (via_merged) *via_merged = s == kNoSlot;
   if (s == kNoSlot) {
     uint32_t lo = 0, hi = G.n;
     while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (G.from[mid] < *taxon) lo = mid + 1; else hi = mid; }
@@ -192,6 +194,69 @@ KJF_HD bool entry_at(const uint8_t *text, uint64_t a, uint64_t e, uint64_t p, ui
   for (uint64_t q = p + 1; q < e; q++)
     if (text[q] == ' ') { *acc_end = q; return true; }
   return false;
+}
+
+// ---- kaiju-convertRefSeq ------------------------------------------------------------------------------------------
+// The second rule set (kRulesRefSeq): kaiju-convertRefSeq.cpp:145-262 of the reference, observed on the unmodified tool
+// (tests/golden/refseq/).  What it shares with kaiju-convertNR - lines, the include walk, the letters, the '\n' per record, the
+// overflow rule - is the code above and below; what differs:
+//   map       two columns, accession.version '\t' taxon.  The first line is skipped, empty lines are skipped.  t = find('\t'):
+//             a line without a tab inserts nothing (there it is a key).  The line must begin with the three bytes "WP_"
+//             (observed: "wp_", "NP_", "XP_" insert nothing; a "WP_" line has t >= 3).  The taxon is strtoul(c_str() + t + 1),
+//             field_strtoul as it is; ULONG_MAX and 0 insert nothing, so a four-column line ("WP_1\tWP_1.1\t562\t9" parses
+//             "WP_1.1": 0) inserts nothing.  A taxon that is a node: the key is [0, t).  A taxon that is no node but that
+//             `merged` maps to a node: the key is [0, t - 1) - substr(0, start - 1), the accession loses its last byte (observed:
+//             "WP_123\t666" is found as "WP_12", "WP_\t666" as "WP").  Neither: nothing.  emplace: the first line that inserts a
+//             key wins, whichever of the two forms gave the key ("WP_12\t562" in front of "WP_123\t666": 562)
+//   header    the accession is [1, first space); a header without a space is dropped without a lookup.  No loop over '\x01':
+//             it is a byte of the accession or of the description like any other.  Found in the map: the record's taxon is the
+//             entry's; not found: dropped.  No LCA, no excluded set
+//   output    '>' [accession '_'] taxon '\n' letters '\n' as above; -a writes the accession looked up
+//   counters  n_entries: headers with a space; n_hits: those found; dropped_excluded and dropped_no_lca stay 0
+// Passes: those above, with `entries` replaced by `first`: one lane per record reads its header in 16-byte chunks from the
+// line start up to the first space or the line end, one map_find, one find_slot, plain stores.
+constexpr int kRulesNr = 0, kRulesRefSeq = 1;
+
+// line [a, e) of the map file, a < e: the key and the node's id, or !valid
+KJF_HD MapLine refseq_map_line(const uint8_t *text, uint64_t a, uint64_t e, const Tree &T, const Merged &G) {
+  MapLine L{a, e, 0, false};
+  uint64_t t;
+  if (!kjm::find_tabs(text, a, e, 1, &t)) return L;
+  if (e - a < 3 || text[a] != 'W' || text[a + 1] != 'P' || text[a + 2] != '_') return L;
+  uint64_t ze = t + 1;                                         // (strtoul reads a C string: a NUL ends it)
+  while (ze < e && text[ze]) ze++;
+  L.taxon = field_strtoul(text, t + 1, ze);
+  if (L.taxon == kSkip || L.taxon == 0) return L;
+  uint32_t slot;
+  bool via_merged;
+  if (!resolve_taxon(T, G, &L.taxon, &slot, &via_merged)) return L;
+  L.key_end = via_merged ? t - 1 : t;                          // (t >= a + 3)
+  L.valid = true;
+  return L;
+}
+
+// the first space of the header line [a, e) behind its '>', e where there is none
+KJF_HD uint64_t first_space(const uint8_t *text, uint64_t a, uint64_t e) {
+  for (uint64_t c = (a + 1) / kChunk; c * kChunk < e; c++) {
+    const uint32_t m = kji::eq_mask(kji::load_chunk(text, c), ' ') & kji::range_mask(c * kChunk, a + 1, e);
+    if (m) return c * kChunk + kji::ctz16(m);
+  }
+  return e;
+}
+struct First { uint32_t slot, first; bool entry, hit; };       // slot, first: kNone without a hit
+// the one entry of the header line [a, e): is there one, does the map hold it, the slot of its taxon
+KJF_HD First first_entry(const uint8_t *text, uint64_t a, uint64_t e, const Map &M, const Tree &T) {
+  First F{kNone, kNone, false, false};
+  const uint64_t sp = first_space(text, a, e);
+  if (sp >= e) return F;
+  F.entry = true;
+  uint32_t probes;
+  const uint8_t *ent = map_find(M, text + a + 1, (uint32_t)(sp - a - 1), &probes);
+  if (!ent || entry_taxon(ent) == 0) return F;
+  const uint32_t slot = kjm::find_slot(T, entry_taxon(ent));
+  if (slot == kNoSlot) return F;                               // (the map holds nodes only)
+  F.slot = slot; F.first = (uint32_t)(a + 1); F.hit = true;
+  return F;
 }
 
 // ---- the tree -----------------------------------------------------------------------------------------------------
@@ -360,6 +425,7 @@ struct kaiju_gpu_accmap;
 struct kaiju_gpu_taxonomy;
 #pragma GCC visibility push(hidden)
 kjc::Map kj_accmap_view(const kaiju_gpu_accmap *m, const kaiju_gpu_taxonomy **tax, int *device);
+int kj_accmap_rules(const kaiju_gpu_accmap *m);               // kRulesNr or kRulesRefSeq: what its lines were parsed by
 #pragma GCC visibility pop
 #endif
 
