@@ -19,6 +19,13 @@
 // Round h -> 2h: only the suffixes that are not final are ACTIVE; they are kept as a list in rank order.  Sort the list by
 // (rank[p] << 32 | rank[p + h]), flag the heads, write the new ranks, drop what became final.
 //
+// Two instantiations.  NARROW: positions, ranks and list indexes in 32 bits, texts below 0xf0000000 symbols (ss_tlen_ok).
+// WIDE: all of them in 64 bits, tlen + rank_bias < 2^40 (ss_tlen_ok_wide).  The round key (rank[p], rank[p + h]) then has up to
+// 80 bits and is a pair (SsKeyW), sorted in two stable passes: by rank[p + h], then by rank[p]; the scan item is a pair of
+// 64-bit list indexes (SsScanItemW).  The wide functions are overloads of the narrow ones on those types, next to them below.
+// rank_bias (wide only, 0 in the product): every rank is bias + what it is above, so that a text of a few thousand symbols
+// carries ranks, round keys and rank comparisons beyond 2^32 through the real kernels; the scatter subtracts it again.
+//
 // INVARIANT of the load rank[p + h]: an active suffix never has its terminator within its first h symbols (h symbols have
 // been compared, and a suffix whose compared part holds its terminator is final: in round 1 by the head rule, later because
 // rank[p + h] is then the rank of a final suffix, which nobody shares).  So p + h lies inside p's own sequence, at most on its
@@ -47,8 +54,10 @@ enum {
   KJ_SS_STATS_ROUNDS = 16
 };
 
-// 32-bit positions only: the host builder's own boundary for its 32-bit instantiation
+// the narrow instantiation: the host builder's own boundary for its 32-bit instantiation
 KJ_SS_HD bool ss_tlen_ok(uint64_t tlen) { return tlen < 0xf0000000ull; }
+// the wide one: every rank, bias included, below 2^40 (room for 5-byte storage, which is not used today)
+KJ_SS_HD bool ss_tlen_ok_wide(uint64_t tlen_plus_bias) { return tlen_plus_bias < (1ull << 40); }
 
 // text bytes on the device: rounded up to a lane's load, plus the look-ahead
 KJ_SS_HD uint64_t ss_text_alloc(uint64_t tlen) { return ((tlen + KJ_SS_LANE_BYTES - 1) / KJ_SS_LANE_BYTES) * KJ_SS_LANE_BYTES + KJ_SS_TEXT_PAD; }
@@ -58,6 +67,16 @@ KJ_SS_HD uint64_t ss_text_alloc(uint64_t tlen) { return ((tlen + KJ_SS_LANE_BYTE
 KJ_SS_HD uint64_t ss_scratch_bytes(uint64_t tlen, uint64_t nsuf) {
   const uint64_t n = nsuf ? nsuf : 1, ntiles = (tlen + KJ_SS_TILE - 1) / KJ_SS_TILE + 1;
   return ss_text_alloc(tlen) + 4 * (tlen + 1) + 16 * n + 8 * n + 4 * n + 4 * ntiles + 6 * 256;
+}
+
+// the wide instantiation: text, ranks (8), five arrays of 8 bytes per suffix in one slab - keys x 2, positions x 2, the active
+// list; the scan items of 16 bytes lie over a free key buffer and the active list, KJ_SS_WIDE_ALIGN keeps the five apart - and
+// 64-bit tile counts and bases.  49 bytes per symbol and the radix sort's and the scans' temporary storage.
+enum { KJ_SS_WIDE_ALIGN = 256 };
+KJ_SS_HD uint64_t ss_wide_stride(uint64_t nsuf) { return ((8 * (nsuf ? nsuf : 1) + KJ_SS_WIDE_ALIGN - 1) / KJ_SS_WIDE_ALIGN) * KJ_SS_WIDE_ALIGN; }
+KJ_SS_HD uint64_t ss_scratch_bytes_wide(uint64_t tlen, uint64_t nsuf) {
+  const uint64_t ntiles = (tlen + KJ_SS_TILE - 1) / KJ_SS_TILE + 1;
+  return ss_text_alloc(tlen) + 8 * (tlen + 1) + 5 * ss_wide_stride(nsuf) + 16 * ntiles + 6 * 256;
 }
 
 // the largest h a round may be asked to run with: beyond it an active suffix is an internal error
@@ -105,15 +124,38 @@ KJ_SS_HD uint64_t ss_round_key(const uint32_t *rank, uint32_t p, uint64_t h, uin
   const uint32_t r2 = q < tlen ? rank[q] : 0u;        // (never out of range: the invariant above)
   return ((uint64_t)rank[p] << 32) | r2;
 }
+// ... wide: a pair; the sort takes lo first and hi second, both stable
+struct SsKeyW { uint64_t hi, lo; };                   // rank[p], rank[p + h]
+KJ_SS_HD uint64_t ss_rank_ahead(const uint64_t *rank, uint64_t p, uint64_t h, uint64_t tlen) {
+  const uint64_t q = p + h;
+  return q < tlen ? rank[q] : 0ull;                   // (never out of range: the invariant above)
+}
+KJ_SS_HD SsKeyW ss_round_key(const uint64_t *rank, uint64_t p, uint64_t h, uint64_t tlen) {
+  const SsKeyW k = {rank[p], ss_rank_ahead(rank, p, h, tlen)};
+  return k;
+}
 // round h: entry i of the sorted list starts a group of the old order / of the new one
 KJ_SS_HD bool ss_head_old(uint64_t i, uint64_t key_prev, uint64_t key) { return i == 0 || (key >> 32) != (key_prev >> 32); }
 KJ_SS_HD bool ss_head_new(uint64_t i, uint64_t key_prev, uint64_t key) { return i == 0 || key != key_prev; }
+KJ_SS_HD bool ss_head_old(uint64_t i, SsKeyW key_prev, SsKeyW key) { return i == 0 || key.hi != key_prev.hi; }
+KJ_SS_HD bool ss_head_new(uint64_t i, SsKeyW key_prev, SsKeyW key) { return i == 0 || key.hi != key_prev.hi || key.lo != key_prev.lo; }
 // what the inclusive scan runs over: (index of the last old head) << 32 | index of the last new head, both maxima
 KJ_SS_HD uint64_t ss_scan_item(uint32_t i, bool head_old, bool head_new) { return ((uint64_t)(head_old ? i : 0u) << 32) | (head_new ? i : 0u); }
 struct SsScanMax {
   KJ_SS_HD uint64_t operator()(uint64_t a, uint64_t b) const {
     const uint64_t ah = a >> 32, bh = b >> 32, al = a & 0xffffffffull, bl = b & 0xffffffffull;
     return ((ah > bh ? ah : bh) << 32) | (al > bl ? al : bl);
+  }
+};
+struct SsScanItemW { uint64_t old_head, new_head; };   // ... wide: the two maxima side by side
+KJ_SS_HD SsScanItemW ss_scan_item_wide(uint64_t i, bool head_old, bool head_new) {
+  const SsScanItemW s = {head_old ? i : 0ull, head_new ? i : 0ull};
+  return s;
+}
+struct SsScanMaxW {
+  KJ_SS_HD SsScanItemW operator()(SsScanItemW a, SsScanItemW b) const {
+    const SsScanItemW s = {a.old_head > b.old_head ? a.old_head : b.old_head, a.new_head > b.new_head ? a.new_head : b.new_head};
+    return s;
   }
 };
 // the new rank of entry i: round 1 counts from nseq, round h from the rank of the old group (the group's members are all
@@ -124,6 +166,16 @@ KJ_SS_HD uint32_t ss_rank_round(uint64_t key, uint64_t scanned) { return (uint32
 KJ_SS_HD bool ss_is_final(uint64_t i, uint64_t n, uint64_t scanned, uint64_t scanned_next) {
   return (uint32_t)scanned == (uint32_t)i && (i + 1 == n || (uint32_t)scanned_next == (uint32_t)(i + 1));
 }
+
+// ... wide: first_rank = rank_bias + nseq
+KJ_SS_HD uint64_t ss_rank_first(uint64_t first_rank, SsScanItemW scanned) { return first_rank + scanned.new_head; }
+KJ_SS_HD uint64_t ss_rank_round(SsKeyW key, SsScanItemW scanned) { return key.hi + (scanned.new_head - scanned.old_head); }
+KJ_SS_HD bool ss_is_final(uint64_t i, uint64_t n, SsScanItemW scanned, SsScanItemW scanned_next) {
+  return scanned.new_head == i && (i + 1 == n || scanned_next.new_head == i + 1);
+}
+// round 1: the letters in front of a lane's first byte = the output index of its first letter (tile_base: letters in front of
+// the lane's tile, before: in front of its wavefront inside the tile, inc - cnt: in front of the lane inside the wavefront)
+KJ_SS_HD uint64_t ss_lane_base(uint64_t tile_base, uint32_t before, uint32_t inc, uint32_t cnt) { return tile_base + before + inc - cnt; }
 
 // ---- the driver (sufsort.hip; host side, linked into libkaiju_mkfmi_gpu.so only) -------------------------------------------
 #ifdef __cplusplus
@@ -142,6 +194,10 @@ struct SsKeep {
 int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
                            SsKeep *keep, std::string &err);
 uint64_t kj_sufsort_need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t *temp_bytes_out);
+// the wide instantiation: 64-bit positions, tlen + rank_bias < 2^40 (ss_tlen_ok_wide); rank_bias = 0 outside the tests
+int kj_sufsort_device_wide(const uint8_t *text, uint64_t tlen, int device_id, uint64_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                           uint64_t rank_bias, std::string &err);
+uint64_t kj_sufsort_need_bytes_wide(uint64_t tlen, uint64_t nsuf, uint64_t rank_bias, uint64_t *temp_bytes_out);
 #endif
 
 #endif

@@ -19,7 +19,8 @@
 //     with the code table of find_startLcode (compactfmi.c:108-150).
 // Suffixes are sorted bucket-wise (first three symbols) with std::sort on a word-at-a-time
 // comparator, buckets in parallel (sort_suffixes_host) - or, compiled with -DKAIJU_MKFMI_GPU into
-// libkaiju_mkfmi_gpu.so and asked to, on a GPU (sort_suffixes_device: kj_sufsort.h, sufsort.hip).
+// libkaiju_mkfmi_gpu.so and asked to, on a GPU (sort_suffixes_device: kj_sufsort.h, sufsort.hip; 32-bit positions below
+// 0xf0000000 bytes of FASTA, 64-bit positions from there on).
 // Everything behind the sorted suffix array - BWT of the file, sequence ranks, replication, samples, checkpoints, byte coding -
 // fills one struct of arrays (FmiArrays) from which the file is written: stages_host, the loops below, or, in
 // libkaiju_mkfmi_gpu.so and asked to, stages_device (kj_fmibuild.h, fmibuild.hip), which sorts on the GPU as well and leaves
@@ -311,15 +312,18 @@ int sort_suffixes_host(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, u
 }
 
 #ifdef KAIJU_MKFMI_GPU
-// on the device (sufsort.hip): 32-bit positions, widened here for the 64-bit instantiation
+// on the device (sufsort.hip).  The 32-bit builder: the narrow sort.  The 64-bit builder: the wide sort straight into SA when the
+// file needs it (wide: build_any decides), else - KAIJU_MKFMI_FORCE64 on a small file - the narrow sort, widened here
 template <class I>
-int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, int device_id, RawArr<I> &SA, BuildClock &bc,
+int sort_suffixes_device(const RawArr<uint8_t> &T, uint64_t tlen, uint64_t nsuf, int device_id, bool wide, RawArr<I> &SA, BuildClock &bc,
                          kaiju_sufsort_stats *stats_out = nullptr) {
   uint64_t n = 0;
   int rc;
   kaiju_sufsort_stats st;
   if (sizeof(I) == 4) {
     rc = kj_sufsort_device(T.data(), tlen, device_id, reinterpret_cast<uint32_t *>(SA.data()), &n, &st, g_err);
+  } else if (wide) {
+    rc = kj_sufsort_device_wide(T.data(), tlen, device_id, reinterpret_cast<uint64_t *>(SA.data()), &n, &st, 0, g_err);
   } else {
     RawArr<uint32_t> sa32(nsuf);
     rc = kj_sufsort_device(T.data(), tlen, device_id, sa32.data(), &n, &st, g_err);
@@ -547,8 +551,9 @@ int stages_host(const uint8_t *T, const std::vector<uint64_t> &starts, const std
 }
 
 #ifdef KAIJU_MKFMI_GPU
-// on the device (kj_fmibuild.h, fmibuild.hip): the sort and the five passes; SA never comes down.  Positions on the device are
-// 32-bit, so both instantiations of the builder take these arrays as they are.
+// on the device (kj_fmibuild.h, fmibuild.hip): the narrow sort and the five passes; SA never comes down.  Positions in these
+// stages are 32-bit (build_any refuses them where the wide sort is chosen), so both instantiations of the builder take these
+// arrays as they are.
 int stages_device(const uint8_t *T, const std::vector<uint64_t> &lens, int device_id, int recode, BuildClock &bc, FmiArrays &A,
                   kaiju_fmi_build_stats *stats) {
   const FbPlan &P = A.P;
@@ -602,7 +607,8 @@ int stages_device(const uint8_t *T, const std::vector<uint64_t> &lens, int devic
 // X_<copy_taxids[(i + t) % n]>, so that the copies do not all carry one taxon.
 template <class I>
 int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t copies = 1, const uint64_t *copy_taxids = nullptr,
-          uint32_t n_copy_taxids = 0, int device_id = -1, int stages = KAIJU_FMI_STAGES_HOST, kaiju_fmi_build_stats *stats = nullptr) {
+          uint32_t n_copy_taxids = 0, int device_id = -1, int stages = KAIJU_FMI_STAGES_HOST, kaiju_fmi_build_stats *stats = nullptr,
+          bool device_wide = false) {
   // alphabet of kaiju-makedb:373 with the terminator in front (mkbwt.c:read_alphabet)
   const char alphabet[] = "*ACDEFGHIKLMNPQRSTVWY";
   const int alen = 21;
@@ -645,7 +651,7 @@ int build(const char *faa, const char *out, int threads, int chpt_exp, uint64_t 
     RawArr<I> SA(nsuf);
     int rc;
 #ifdef KAIJU_MKFMI_GPU
-    if (device_id >= 0) rc = sort_suffixes_device<I>(T, tlen, nsuf, device_id, SA, bc, stats ? &stats->sort : nullptr);
+    if (device_id >= 0) rc = sort_suffixes_device<I>(T, tlen, nsuf, device_id, device_wide, SA, bc, stats ? &stats->sort : nullptr);
     else
 #endif
       rc = sort_suffixes_host<I>(T, tlen, nsuf, nt, SA, bc);
@@ -726,12 +732,16 @@ int build_any(const char *faa_path, const char *out_fmi_path, int threads, int c
   const off_t sz = ftello(fp);
   fclose(fp);
   const bool narrow = (uint64_t)sz < 0xf0000000ull;
-  if (device_id >= 0 && !narrow) {
-    g_err = "suffix sort on the device: 32-bit positions only (file of " + std::to_string((uint64_t)sz) + " bytes); kaiju_build_fmi, the host builder, sorts with 64-bit positions";
+  // on a device a big file takes the wide sort (64-bit positions, kj_sufsort.h); KAIJU_MKFMI_DEVICE_WIDE=1 with
+  // KAIJU_MKFMI_FORCE64: the wide sort on a small file - tests/test_gpu_sufsort_wide.py
+  const bool device_wide = device_id >= 0 && (!narrow || getenv("KAIJU_MKFMI_DEVICE_WIDE"));
+  if (device_wide && stages == KAIJU_FMI_STAGES_DEVICE) {
+    g_err = "stages on the device: 32-bit positions only (file of " + std::to_string((uint64_t)sz) + " bytes" + (narrow ? ", KAIJU_MKFMI_DEVICE_WIDE set" : "") +
+            "); stages = host takes the suffix array of the wide device sort";
     return KAIJU_GPU_ERR_ARG;
   }
   if (narrow && !getenv("KAIJU_MKFMI_FORCE64")) return build<uint32_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats);
-  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats);
+  return build<uint64_t>(faa_path, out_fmi_path, threads, chpt_exp, copies, copy_taxids, n_copy_taxids, device_id, stages, stats, device_wide);
 }
 
 // the arrays of a text (kaiju_fmi_arrays_*): sizes only, or the host / the device stages into the caller's buffers
@@ -739,7 +749,10 @@ int arrays_any(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp
                kaiju_fmi_build_stats *stats, bool sizes_only) {
   if (stats) memset(stats, 0, sizeof *stats);
   if (!text || !a || tlen == 0 || chpt_exp < 0 || chpt_exp > 20 || copies < 1) { g_err = "fmi arrays: bad argument"; return KAIJU_GPU_ERR_ARG; }
-  if (tlen >= 0xf0000000ull) { g_err = "fmi arrays: 32-bit positions only (text of " + std::to_string(tlen) + " symbols)"; return KAIJU_GPU_ERR_ARG; }
+  if (tlen >= 0xf0000000ull) {
+    g_err = "fmi arrays: 32-bit positions only (text of " + std::to_string(tlen) + " symbols); the file builders take such a text, on a device with stages = host";
+    return KAIJU_GPU_ERR_ARG;
+  }
   if (text[tlen - 1] != 0) { g_err = "fmi arrays: the text does not end with a terminator"; return KAIJU_GPU_ERR_ARG; }
   std::vector<uint64_t> starts, lens;
   uint64_t maxlen = 0;
@@ -835,6 +848,16 @@ extern "C" int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int 
     if (top > 20) { g_err = "suffix sort on the device: symbol codes are 0 .. 20"; return KAIJU_GPU_ERR_ARG; }
   }
   return kj_sufsort_device(text, tlen, device_id, sa_out, n_out, stats, g_err);
+}
+
+extern "C" int kaiju_suffix_sort_device_wide(const uint8_t *text, uint64_t tlen, int device_id, uint64_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                                             uint64_t rank_bias) {
+  if (text && tlen < (1ull << 40) && rank_bias < (1ull << 40) && ss_tlen_ok_wide(tlen + rank_bias)) {      // (likewise)
+    uint8_t top = 0;
+    for (uint64_t p = 0; p < tlen; p++) top = std::max(top, text[p]);
+    if (top > 20) { g_err = "suffix sort on the device: symbol codes are 0 .. 20"; return KAIJU_GPU_ERR_ARG; }
+  }
+  return kj_sufsort_device_wide(text, tlen, device_id, sa_out, n_out, stats, rank_bias, g_err);
 }
 #endif
 

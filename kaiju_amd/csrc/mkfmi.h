@@ -53,18 +53,26 @@ typedef struct kaiju_sufsort_stats {
   float ms_sort;                                   /* HIP events around upload, sort and download */
   float reserved2;
 } kaiju_sufsort_stats;
-/* kaiju_build_fmi / kaiju_build_fmi_replicated with the suffixes sorted on device `device_id`; the same bytes.  32-bit positions
-   only: a file of 0xf0000000 bytes and more is KAIJU_GPU_ERR_ARG (kaiju_build_fmi, the host builder, has the 64-bit sort); under
-   KAIJU_MKFMI_FORCE64 the device sorts in 32 bits and the builder widens the result.  A device_id that does not exist:
-   KAIJU_GPU_ERR_ARG.  The sort's scratch (about 33 bytes per symbol, kj_sufsort.h: ss_scratch_bytes) is compared with the free
-   device memory before anything is allocated: KAIJU_GPU_ERR_NOMEM. */
+/* kaiju_build_fmi / kaiju_build_fmi_replicated with the suffixes sorted on device `device_id`; the same bytes.  A file below
+   0xf0000000 bytes is sorted with 32-bit positions, a bigger one with 64-bit positions (the wide instantiation of the same
+   sort, kj_sufsort.h; ranks below 2^40).  Under KAIJU_MKFMI_FORCE64 on a small file the device sorts in 32 bits and the builder
+   widens the result, with KAIJU_MKFMI_DEVICE_WIDE=1 as well it runs the wide sort (a test switch).  A device_id that does not
+   exist: KAIJU_GPU_ERR_ARG.  The sort's scratch - about 33 bytes per symbol narrow (ss_scratch_bytes), 49 bytes per symbol wide
+   (ss_scratch_bytes_wide: text 1, ranks 8, keys 2 x 8, positions 2 x 8, active list 8), plus rocPRIM's temporary storage - is
+   compared with the free device memory before anything is allocated: KAIJU_GPU_ERR_NOMEM with both numbers. */
 int kaiju_build_fmi_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, int device_id);
 int kaiju_build_fmi_replicated_device(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
                                       const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id);
 /* The sorter alone.  Host pointers, blocking: text up, positions down.  text[0, tlen): codes 0 .. 20, the last one 0;
    sa_out: room for tlen minus the number of terminators; *n_out: how many were written.  tlen >= 0xf0000000 is refused
-   (KAIJU_GPU_ERR_ARG) before the text is looked at.  stats may be NULL. */
+   (KAIJU_GPU_ERR_ARG) before the text is looked at: sa_out has 32-bit positions.  stats may be NULL. */
 int kaiju_suffix_sort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats);
+/* The same with 64-bit positions: always the wide instantiation, whatever the length.  tlen + rank_bias >= 2^40 is refused
+   (KAIJU_GPU_ERR_ARG) before the text is looked at.  rank_bias is a test hook and 0 otherwise: every rank inside the sort is
+   rank_bias higher, so that a small text carries ranks and round keys beyond 2^32 through the kernels; the result does not
+   depend on it. */
+int kaiju_suffix_sort_device_wide(const uint8_t *text, uint64_t tlen, int device_id, uint64_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                                  uint64_t rank_bias);
 
 
 /* ---- the arrays of a .fmi from a text, without a file (both libraries) ------------------------------------------------------
@@ -102,11 +110,13 @@ typedef struct kaiju_fmi_build_stats {
    kaiju_build_fmi_replicated_device does.  KAIJU_FMI_STAGES_DEVICE: on the device; the same bytes.  Any other value:
    KAIJU_GPU_ERR_ARG.  The device memory needed - the sort's scratch that is kept plus tlen * copies bytes of BWT, samples,
    index2 and piece counts (kj_fmibuild.h: fb_scratch_bytes) - is compared with the free device memory before anything is
-   allocated: KAIJU_GPU_ERR_NOMEM with both numbers, and no output file.  stats may be NULL. */
+   allocated: KAIJU_GPU_ERR_NOMEM with both numbers, and no output file.  The device stages have 32-bit positions: where the wide
+   sort would be chosen (a file of 0xf0000000 bytes and more, or KAIJU_MKFMI_DEVICE_WIDE set) KAIJU_FMI_STAGES_DEVICE is
+   KAIJU_GPU_ERR_ARG, without an output file; stages = host builds such a file.  stats may be NULL. */
 int kaiju_build_fmi_device_ex(const char *faa_path, const char *out_fmi_path, int threads, int chpt_exp, uint64_t copies,
                               const uint64_t *copy_taxids, uint32_t n_copy_taxids, int device_id, int stages, kaiju_fmi_build_stats *stats);
 /* kaiju_fmi_arrays_host with the sort and all five stages on device `device_id`: the analogue of kaiju_suffix_sort_device.
-   Host pointers, blocking.  stats may be NULL. */
+   Host pointers, blocking.  32-bit positions: tlen >= 0xf0000000 is KAIJU_GPU_ERR_ARG.  stats may be NULL. */
 int kaiju_fmi_arrays_device(const uint8_t *text, uint64_t tlen, uint64_t copies, int chpt_exp, int device_id, int recode, kaiju_fmi_arrays *a,
                             kaiju_fmi_build_stats *stats);
 

@@ -1,6 +1,6 @@
 // sufsort.hip - the suffix sort of the index builder on the device (gfx950): prefix doubling over ranks, kj_sufsort.h has the
 // definition, the rank invariant and the per-lane logic.  Here: the kernels and the driver loop.  The stable radix sort of
-// (64-bit key, 32-bit position) and the prefix scans are rocPRIM's; everything else is below.
+// (64-bit key, position) and the prefix scans are rocPRIM's; everything else is below.
 //
 // Passes.  Round 1: k_ss_count (letters per tile of 4096 text bytes) -> exclusive scan of the tile counts -> k_ss_keys (keys
 // of 12 symbols and positions in position order, sequence numbers as ranks of the terminators) -> radix sort, 60 bits.
@@ -9,12 +9,23 @@
 // of the flags -> k_ss_compact (the next active list) -> ONE read-back: the active count.  At the end k_ss_scatter writes
 // SA[rank[p] - nseq] = p.  All memory is allocated in front of round 1 (ss_scratch_bytes + rocPRIM's temporary storage,
 // compared with the free HBM first).
+//
+// Two instantiations of all of it on the position type P (kj_sufsort.h): uint32_t, the narrow one, and uint64_t, the wide one,
+// in which positions, ranks, list indexes, tile bases, flags and the active count have 64 bits.  The wide round key
+// (rank[p], rank[p + h]) does not fit a 64-bit radix key, so a wide round sorts twice, both times stable and over
+// bits(rank_bias + tlen) bits: k_ss_round_keys writes rank[p + h], sort, k_ss_round_keys_hi writes rank[p] of the sorted
+// positions, sort.  Behind that the key buffer holds rank[p]; k_ss_heads loads rank[p + h] again for an entry and its
+// predecessor.  The wide scan item has 16 bytes and lies over the free key buffer and the active list, which is dead between
+// k_ss_round_keys and k_ss_compact (the slab below keeps the two side by side).
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "kj_sufsort.h"
 #include "mkfmi.h"
@@ -23,9 +34,14 @@ static_assert((int)KJ_SS_STATS_ROUNDS == (int)KAIJU_SUFSORT_STATS_ROUNDS, "kaiju
 
 namespace {
 
+template <class P> struct SsTypes;
+template <> struct SsTypes<uint32_t> { typedef uint64_t Item; typedef SsScanMax Scan; static constexpr bool wide = false; };
+template <> struct SsTypes<uint64_t> { typedef SsScanItemW Item; typedef SsScanMaxW Scan; static constexpr bool wide = true; };
+
 // ---- kernels -------------------------------------------------------------------------------------------------------------
 // text is allocated to ss_text_alloc(tlen) bytes, zero behind tlen: lane g reads bytes [16 g, 16 g + 32)
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_count(const uint4 *__restrict__ text, uint64_t nlanes, uint32_t *__restrict__ tile_count) {
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_count(const uint4 *__restrict__ text, uint64_t nlanes, P *__restrict__ tile_count) {
   const uint64_t g = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x;
   uint32_t c = 0;
   if (g < nlanes) {
@@ -43,9 +59,11 @@ __global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_count(const uint4 *__restric
   }
 }
 
+// rank_bias: 0 in the narrow instantiation
+template <class P>
 __global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_keys(const uint4 *__restrict__ text, uint64_t nlanes, uint64_t tlen, uint64_t nsuf,
-                                                        const uint32_t *__restrict__ tile_base, uint64_t *__restrict__ keys,
-                                                        uint32_t *__restrict__ vals, uint32_t *__restrict__ rank) {
+                                                        const P *__restrict__ tile_base, uint64_t rank_bias, uint64_t *__restrict__ keys,
+                                                        P *__restrict__ vals, P *__restrict__ rank) {
   const uint64_t g = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x;
   uint64_t k[KJ_SS_LANE_BYTES];
   uint32_t letters = 0;
@@ -66,72 +84,113 @@ __global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_keys(const uint4 *__restrict
   uint32_t before = 0;
   for (int w = 0; w < wave; w++) before += part[w];
   if (g >= nlanes) return;
-  uint64_t o = (uint64_t)tile_base[blockIdx.x] + before + inc - cnt;     // letters in front of the lane's first byte
+  uint64_t o = ss_lane_base(tile_base[blockIdx.x], before, inc, cnt);      // letters in front of the lane's first byte
   const uint64_t p0 = g * KJ_SS_LANE_BYTES;
 #pragma unroll
   for (int j = 0; j < KJ_SS_LANE_BYTES; j++) {
     const uint64_t p = p0 + j;
     if ((letters >> j) & 1u) {
-      if (o < nsuf) { keys[o] = k[j]; vals[o] = (uint32_t)p; }
+      if (o < nsuf) { keys[o] = k[j]; vals[o] = (P)p; }
       o++;
     } else if (p < tlen) {
-      rank[p] = (uint32_t)(p - o);          // a terminator: its sequence number = the terminators in front of it
+      rank[p] = (P)(rank_bias + (p - o));    // a terminator: its sequence number = the terminators in front of it
     }
   }
 }
 
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_round_keys(const uint32_t *__restrict__ act, uint64_t m, const uint32_t *__restrict__ rank,
-                                                              uint64_t h, uint64_t tlen, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+// narrow: the whole key; wide: its low part rank[p + h], the key of the first of the two sorts
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_round_keys(const P *__restrict__ act, uint64_t m, const P *__restrict__ rank, uint64_t h,
+                                                              uint64_t tlen, uint64_t *__restrict__ keys, P *__restrict__ vals) {
   for (uint64_t i = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
-    const uint32_t p = act[i];
-    keys[i] = p < tlen ? ss_round_key(rank, p, h, tlen) : 0ull;
+    const P p = act[i];
+    if constexpr (SsTypes<P>::wide) keys[i] = p < tlen ? ss_rank_ahead(rank, p, h, tlen) : 0ull;
+    else keys[i] = p < tlen ? ss_round_key(rank, p, h, tlen) : 0ull;
     vals[i] = p;
   }
 }
 
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_heads(const uint64_t *__restrict__ keys, uint64_t m, int first, uint64_t *__restrict__ items) {
+// wide: the high part rank[p] of the positions as the first sort left them, the key of the second sort
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_round_keys_hi(const uint64_t *__restrict__ vals, uint64_t m, const uint64_t *__restrict__ rank,
+                                                                 uint64_t tlen, uint64_t *__restrict__ keys) {
   for (uint64_t i = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
-    const uint64_t k = keys[i], kp = i ? keys[i - 1] : 0ull;
-    items[i] = first ? ss_scan_item((uint32_t)i, false, ss_head_first(i, kp, k))
-                     : ss_scan_item((uint32_t)i, ss_head_old(i, kp, k), ss_head_new(i, kp, k));
+    const uint64_t p = vals[i];
+    keys[i] = p < tlen ? rank[p] : 0ull;
   }
 }
 
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_ranks(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                         const uint64_t *__restrict__ scanned, uint64_t m, int first, uint32_t nseq, uint64_t tlen,
-                                                         uint32_t *__restrict__ rank, uint32_t *__restrict__ flags) {
+// keys: round 1 the keys of 12 symbols; round h narrow the whole key, wide rank[p] (rank[p + h] is loaded again through vals)
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_heads(const uint64_t *__restrict__ keys, const P *__restrict__ vals, const P *__restrict__ rank,
+                                                         uint64_t m, int first, uint64_t h, uint64_t tlen,
+                                                         typename SsTypes<P>::Item *__restrict__ items) {
   for (uint64_t i = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
-    const uint64_t s = scanned[i], sn = i + 1 < m ? scanned[i + 1] : 0ull;
-    const uint32_t p = vals[i];
-    if (p < tlen) rank[p] = first ? ss_rank_first(nseq, s) : ss_rank_round(keys[i], s);
+    const uint64_t k = keys[i], kp = i ? keys[i - 1] : 0ull;
+    if constexpr (SsTypes<P>::wide) {
+      if (first) {
+        items[i] = ss_scan_item_wide(i, false, ss_head_first(i, kp, k));
+      } else {
+        const SsKeyW key = {k, ss_rank_ahead(rank, vals[i], h, tlen)}, prev = {kp, i ? ss_rank_ahead(rank, vals[i - 1], h, tlen) : 0ull};
+        items[i] = ss_scan_item_wide(i, ss_head_old(i, prev, key), ss_head_new(i, prev, key));
+      }
+    } else {
+      items[i] = first ? ss_scan_item((uint32_t)i, false, ss_head_first(i, kp, k))
+                       : ss_scan_item((uint32_t)i, ss_head_old(i, kp, k), ss_head_new(i, kp, k));
+    }
+  }
+}
+
+// first_rank: the rank of the first letter suffix, rank_bias + nseq
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_ranks(const uint64_t *__restrict__ keys, const P *__restrict__ vals,
+                                                         const typename SsTypes<P>::Item *__restrict__ scanned, uint64_t m, int first,
+                                                         uint64_t first_rank, uint64_t tlen, P *__restrict__ rank, P *__restrict__ flags) {
+  for (uint64_t i = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
+    const typename SsTypes<P>::Item s = scanned[i], sn = i + 1 < m ? scanned[i + 1] : typename SsTypes<P>::Item();
+    const P p = vals[i];
+    if (p < tlen) {
+      if constexpr (SsTypes<P>::wide) {
+        const SsKeyW key = {keys[i], 0ull};
+        rank[p] = first ? ss_rank_first(first_rank, s) : ss_rank_round(key, s);
+      } else {
+        rank[p] = first ? ss_rank_first((uint32_t)first_rank, s) : ss_rank_round(keys[i], s);
+      }
+    }
     flags[i] = ss_is_final(i, m, s, sn) ? 0u : 1u;
   }
 }
 
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_compact(const uint32_t *__restrict__ vals, const uint32_t *__restrict__ incl, uint64_t m,
-                                                           uint32_t *__restrict__ act) {
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_compact(const P *__restrict__ vals, const P *__restrict__ incl, uint64_t m, P *__restrict__ act) {
   for (uint64_t i = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
-    const uint32_t c = incl[i], b = i ? incl[i - 1] : 0u;
+    const P c = incl[i], b = i ? incl[i - 1] : 0u;
     if (c != b && c <= m) act[c - 1] = vals[i];        // (c <= i + 1 by construction)
   }
 }
 
 // rank is allocated to 16 nlanes entries: lane g reads its 16
-__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_scatter(const uint4 *__restrict__ text, const uint4 *__restrict__ rank, uint64_t nlanes,
-                                                           uint32_t nseq, uint64_t nsuf, uint32_t *__restrict__ sa) {
+template <class P>
+__global__ __launch_bounds__(KJ_SS_BLOCK) void k_ss_scatter(const uint4 *__restrict__ text, const P *__restrict__ rank, uint64_t nlanes,
+                                                           uint64_t first_rank, uint64_t nsuf, P *__restrict__ sa) {
   for (uint64_t g = (uint64_t)blockIdx.x * KJ_SS_BLOCK + threadIdx.x; g < nlanes; g += (uint64_t)gridDim.x * KJ_SS_BLOCK) {
     const uint4 t = text[g];
     const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (!tw[q]) continue;
-      const uint4 r = rank[g * 4 + q];
-      const uint32_t rw[4] = {r.x, r.y, r.z, r.w};
+      P rw[4];
+      if constexpr (SsTypes<P>::wide) {
+        const ulonglong2 a = reinterpret_cast<const ulonglong2 *>(rank)[g * 8 + q * 2], b = reinterpret_cast<const ulonglong2 *>(rank)[g * 8 + q * 2 + 1];
+        rw[0] = a.x; rw[1] = a.y; rw[2] = b.x; rw[3] = b.y;
+      } else {
+        const uint4 r = reinterpret_cast<const uint4 *>(rank)[g * 4 + q];
+        rw[0] = r.x; rw[1] = r.y; rw[2] = r.z; rw[3] = r.w;
+      }
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         if (!((tw[q] >> (8 * j)) & 0xffu)) continue;
-        const uint64_t row = (uint64_t)rw[j] - nseq;       // (wraps to a huge value if the rank were below nseq)
-        if (row < nsuf) sa[row] = (uint32_t)(g * KJ_SS_LANE_BYTES + q * 4 + j);
+        const uint64_t row = (uint64_t)rw[j] - first_rank;       // (wraps to a huge value if the rank were below the first letter's)
+        if (row < nsuf) sa[row] = (P)(g * KJ_SS_LANE_BYTES + q * 4 + j);
       }
     }
   }
@@ -162,51 +221,60 @@ int bits_of(uint64_t v) { int b = 0; while (v >> b) ++b; return b; }
     if (e_ != hipSuccess) { err = std::string("suffix sort on the device: ") + #call + ": " + hipGetErrorString(e_); return KAIJU_GPU_ERR_HIP; } \
   } while (0)
 
-size_t sort_temp(uint64_t n, unsigned end_bit) {
+// rocPRIM's temporary storage: asked with the element counts as size_t, which pass 2^32 in the wide instantiation
+template <class P> size_t sort_temp(uint64_t n, unsigned end_bit) {
   rocprim::double_buffer<uint64_t> k(nullptr, nullptr);
-  rocprim::double_buffer<uint32_t> v(nullptr, nullptr);
+  rocprim::double_buffer<P> v(nullptr, nullptr);
   size_t s = 0;
   (void)rocprim::radix_sort_pairs(nullptr, s, k, v, (size_t)n, 0u, end_bit);
   return s;
 }
-size_t scan64_temp(uint64_t n) { size_t s = 0; (void)rocprim::inclusive_scan(nullptr, s, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, SsScanMax()); return s; }
-size_t scan32_temp(uint64_t n) { size_t s = 0; (void)rocprim::inclusive_scan(nullptr, s, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)n, rocprim::plus<uint32_t>()); return s; }
-size_t tile_temp(uint64_t n) { size_t s = 0; (void)rocprim::exclusive_scan(nullptr, s, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>()); return s; }
-
-}  // namespace
-
-int kj_sufsort_check_device(int device_id, std::string &err) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { err = "suffix sort on the device: no HIP device (kaiju_build_fmi is the host builder)"; return KAIJU_GPU_ERR_NO_DEVICE; }
-  if (device_id < 0 || device_id >= n) { err = "suffix sort on the device: device_id " + std::to_string(device_id) + " of " + std::to_string(n) + " devices"; return KAIJU_GPU_ERR_ARG; }
-  return KAIJU_GPU_OK;
+template <class P> size_t scan_items_temp(uint64_t n) {
+  typedef typename SsTypes<P>::Item Item;
+  size_t s = 0;
+  (void)rocprim::inclusive_scan(nullptr, s, (Item *)nullptr, (Item *)nullptr, (size_t)n, typename SsTypes<P>::Scan());
+  return s;
 }
+template <class P> size_t scan_flags_temp(uint64_t n) { size_t s = 0; (void)rocprim::inclusive_scan(nullptr, s, (P *)nullptr, (P *)nullptr, (size_t)n, rocprim::plus<P>()); return s; }
+template <class P> size_t tile_temp(uint64_t n) { size_t s = 0; (void)rocprim::exclusive_scan(nullptr, s, (P *)nullptr, (P *)nullptr, (P)0, (size_t)n, rocprim::plus<P>()); return s; }
 
-int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
-                      std::string &err) {
-  return kj_sufsort_device_keep(text, tlen, device_id, sa_out, n_out, stats, nullptr, err);
+// the bits a round's radix sort runs over.  Narrow: rank[p] above bit 32.  Wide: each of the two sorts over one rank, and every
+// rank, the bias included, is below rank_bias + tlen
+template <class P> unsigned round_bits_of(uint64_t tlen, uint64_t rank_bias) {
+  return SsTypes<P>::wide ? (unsigned)bits_of(rank_bias + tlen) : 32u + (unsigned)bits_of(tlen);
 }
 
 // what one sort allocates (the caller has selected the device: rocPRIM sizes its temporary storage for it)
-uint64_t kj_sufsort_need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t *temp_bytes_out) {
+template <class P> uint64_t need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t rank_bias, uint64_t *temp_bytes_out) {
   const uint64_t n = std::max<uint64_t>(nsuf, 1);
   const uint64_t nlanes = (tlen + KJ_SS_LANE_BYTES - 1) / KJ_SS_LANE_BYTES, ntiles = (nlanes + KJ_SS_BLOCK - 1) / KJ_SS_BLOCK;
   const uint64_t rank_entries = nlanes * KJ_SS_LANE_BYTES;
-  const unsigned round_bits = 32u + (unsigned)bits_of(tlen);
-  const size_t temp_bytes = std::max({sort_temp(n, KJ_SS_KEY_BITS), sort_temp(n, round_bits), scan64_temp(n), scan32_temp(n), tile_temp(ntiles)});
+  const unsigned round_bits = round_bits_of<P>(tlen, rank_bias);
+  const size_t temp_bytes = std::max({sort_temp<P>(n, KJ_SS_KEY_BITS), sort_temp<P>(n, round_bits), scan_items_temp<P>(n), scan_flags_temp<P>(n), tile_temp<P>(ntiles)});
   if (temp_bytes_out) *temp_bytes_out = temp_bytes;
+  if (SsTypes<P>::wide) return ss_scratch_bytes_wide(tlen, nsuf) + 8 * (rank_entries - tlen) + temp_bytes;      // (both tile arrays are in the formula)
   return ss_scratch_bytes(tlen, nsuf) + 4 * (rank_entries - tlen) + temp_bytes + 4 * ntiles;
 }
 
-// keep != nullptr: SA is not downloaded (sa_out may be nullptr); text, rank[], SA, the first key buffer and the temporary
-// storage stay allocated and are handed to the caller, who frees them (hipFree) - also for a text without a suffix, whose
-// terminators still get their ranks
-int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
-                           SsKeep *keep, std::string &err) {
+// keep != nullptr (narrow only): SA is not downloaded (sa_out may be nullptr); text, rank[], SA, the first key buffer and the
+// temporary storage stay allocated and are handed to the caller, who frees them (hipFree) - also for a text without a suffix,
+// whose terminators still get their ranks
+template <class P>
+int sufsort_run(const uint8_t *text, uint64_t tlen, int device_id, P *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats, SsKeep *keep,
+                uint64_t rank_bias, std::string &err) {
+  constexpr bool wide = SsTypes<P>::wide;
+  typedef typename SsTypes<P>::Item Item;
   if (stats) memset(stats, 0, sizeof *stats);
   if (n_out) *n_out = 0;
-  if (!ss_tlen_ok(tlen)) {
-    err = "suffix sort on the device: 32-bit positions only (text of " + std::to_string(tlen) + " symbols); kaiju_build_fmi, the host builder, sorts with 64-bit positions";
+  if (wide) {
+    if (keep) { err = "internal: suffix sort on the device: the wide sort keeps nothing"; return KAIJU_GPU_ERR_ARG; }
+    if (tlen >= (1ull << 40) || rank_bias >= (1ull << 40) || !ss_tlen_ok_wide(tlen + rank_bias)) {
+      err = "suffix sort on the device: 40-bit ranks only (text of " + std::to_string(tlen) + " symbols, rank bias " + std::to_string(rank_bias) +
+            "); kaiju_build_fmi, the host builder, sorts texts of any length";
+      return KAIJU_GPU_ERR_ARG;
+    }
+  } else if (!ss_tlen_ok(tlen)) {
+    err = "suffix sort on the device: 32-bit positions only (text of " + std::to_string(tlen) + " symbols); kaiju_suffix_sort_device_wide sorts with 64-bit positions on the device, kaiju_build_fmi, the host builder, on the host";
     return KAIJU_GPU_ERR_ARG;
   }
   if (!text || tlen == 0 || (!sa_out && !keep)) { err = "suffix sort on the device: no text"; return KAIJU_GPU_ERR_ARG; }
@@ -232,27 +300,45 @@ int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, ui
 
   const uint64_t nlanes = (tlen + KJ_SS_LANE_BYTES - 1) / KJ_SS_LANE_BYTES, ntiles = (nlanes + KJ_SS_BLOCK - 1) / KJ_SS_BLOCK;
   const uint64_t text_bytes = ss_text_alloc(tlen), rank_entries = nlanes * KJ_SS_LANE_BYTES;
-  const unsigned round_bits = 32u + (unsigned)bits_of(tlen);
+  const unsigned round_bits = round_bits_of<P>(tlen, rank_bias);
+  const uint64_t first_rank = rank_bias + nseq;
   uint64_t temp_bytes64 = 0;
-  const uint64_t need = kj_sufsort_need_bytes(tlen, nsuf, &temp_bytes64);
+  const uint64_t need = need_bytes<P>(tlen, nsuf, rank_bias, &temp_bytes64);
   const size_t temp_bytes = (size_t)temp_bytes64;
   size_t free_b = 0, total_b = 0;
   SS_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (getenv("KAIJU_GPU_LOAD_TIMES") && wide)
+    fprintf(stderr, "[kaiju mkfmi]   wide suffix sort: needs %llu bytes of device memory (%.2f per symbol, %llu of them temporary storage), %llu are free\n",
+            (unsigned long long)need, (double)need / (double)tlen, (unsigned long long)temp_bytes64, (unsigned long long)free_b);
   if (need > free_b) {
     err = "suffix sort on the device: needs " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) +
           " MiB are free; kaiju_build_fmi sorts on the host";
     return KAIJU_GPU_ERR_NOMEM;
   }
+  // narrow: an allocation each (some are handed on to the stages behind the sort).  Wide: the five arrays of 8 bytes per suffix
+  // in one slab, key buffer / active list / key buffer / positions / positions, so that whichever key buffer is free lies next
+  // to the active list and the two hold the scan items of 16 bytes
   DevBuf d_text, d_rank, d_k0, d_k1, d_v0, d_v1, d_act, d_tcnt, d_tbase, d_temp;
   SS_HIP(d_text.alloc(text_bytes));
-  SS_HIP(d_rank.alloc(4 * rank_entries));
-  SS_HIP(d_k0.alloc(8 * nsuf));
-  SS_HIP(d_k1.alloc(8 * nsuf));
-  SS_HIP(d_v0.alloc(4 * nsuf));
-  SS_HIP(d_v1.alloc(4 * nsuf));
-  SS_HIP(d_act.alloc(4 * nsuf));
-  SS_HIP(d_tcnt.alloc(4 * ntiles));
-  SS_HIP(d_tbase.alloc(4 * ntiles));
+  SS_HIP(d_rank.alloc(sizeof(P) * rank_entries));
+  uint64_t *k0, *k1;
+  P *v0, *v1, *act;
+  if (wide) {
+    const uint64_t stride = ss_wide_stride(nsuf);
+    SS_HIP(d_k0.alloc(5 * stride));
+    uint8_t *slab = d_k0.as<uint8_t>();
+    k0 = reinterpret_cast<uint64_t *>(slab); act = reinterpret_cast<P *>(slab + stride); k1 = reinterpret_cast<uint64_t *>(slab + 2 * stride);
+    v0 = reinterpret_cast<P *>(slab + 3 * stride); v1 = reinterpret_cast<P *>(slab + 4 * stride);
+  } else {
+    SS_HIP(d_k0.alloc(8 * nsuf));
+    SS_HIP(d_k1.alloc(8 * nsuf));
+    SS_HIP(d_v0.alloc(4 * nsuf));
+    SS_HIP(d_v1.alloc(4 * nsuf));
+    SS_HIP(d_act.alloc(4 * nsuf));
+    k0 = d_k0.as<uint64_t>(); k1 = d_k1.as<uint64_t>(); v0 = d_v0.as<P>(); v1 = d_v1.as<P>(); act = d_act.as<P>();
+  }
+  SS_HIP(d_tcnt.alloc(sizeof(P) * ntiles));
+  SS_HIP(d_tbase.alloc(sizeof(P) * ntiles));
   SS_HIP(d_temp.alloc(temp_bytes));
   Events ev;
   SS_HIP(hipEventCreate(&ev.a));
@@ -261,19 +347,18 @@ int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, ui
   SS_HIP(hipEventRecord(ev.a, st));
   SS_HIP(hipMemsetAsync(d_text.as<uint8_t>() + (text_bytes - KJ_SS_TEXT_PAD - KJ_SS_LANE_BYTES), 0, KJ_SS_TEXT_PAD + KJ_SS_LANE_BYTES, st));
   SS_HIP(hipMemcpyAsync(d_text.p, text, tlen, hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemsetAsync(d_rank.p, 0, 4 * rank_entries, st));
+  SS_HIP(hipMemsetAsync(d_rank.p, 0, sizeof(P) * rank_entries, st));
 
   // ---- round 1 ----
   size_t tb = temp_bytes;
-  k_ss_count<<<(unsigned)ntiles, KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), nlanes, d_tcnt.as<uint32_t>());
+  k_ss_count<P><<<(unsigned)ntiles, KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), nlanes, d_tcnt.as<P>());
   SS_HIP(hipGetLastError());
-  SS_HIP(rocprim::exclusive_scan(d_temp.p, tb, d_tcnt.as<uint32_t>(), d_tbase.as<uint32_t>(), 0u, (size_t)ntiles, rocprim::plus<uint32_t>(), st));
-  k_ss_keys<<<(unsigned)ntiles, KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), nlanes, tlen, nsuf, d_tbase.as<uint32_t>(), d_k0.as<uint64_t>(),
-                                                     d_v0.as<uint32_t>(), d_rank.as<uint32_t>());
+  SS_HIP(rocprim::exclusive_scan(d_temp.p, tb, d_tcnt.as<P>(), d_tbase.as<P>(), (P)0, (size_t)ntiles, rocprim::plus<P>(), st));
+  k_ss_keys<P><<<(unsigned)ntiles, KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), nlanes, tlen, nsuf, d_tbase.as<P>(), rank_bias, k0, v0, d_rank.as<P>());
   SS_HIP(hipGetLastError());
 
-  rocprim::double_buffer<uint64_t> kb(d_k0.as<uint64_t>(), d_k1.as<uint64_t>());
-  rocprim::double_buffer<uint32_t> vb(d_v0.as<uint32_t>(), d_v1.as<uint32_t>());
+  rocprim::double_buffer<uint64_t> kb(k0, k1);
+  rocprim::double_buffer<P> vb(v0, v1);
   uint64_t m = nsuf, h = 0;
   uint32_t rounds = 0;
   while (m != 0) {                                          // (a text without a suffix, kept: no round)
@@ -285,27 +370,37 @@ int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, ui
               std::to_string(maxlen) + ")";
         return KAIJU_GPU_ERR_ARG;
       }
-      k_ss_round_keys<<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(d_act.as<uint32_t>(), m, d_rank.as<uint32_t>(), h, tlen, kb.current(), vb.current());
+      k_ss_round_keys<P><<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(act, m, d_rank.as<P>(), h, tlen, kb.current(), vb.current());
       SS_HIP(hipGetLastError());
     }
     const unsigned end_bit = first ? (unsigned)KJ_SS_KEY_BITS : round_bits;
-    if (sort_temp(m, end_bit) > temp_bytes || scan64_temp(m) > temp_bytes || scan32_temp(m) > temp_bytes) { err = "internal: suffix sort on the device: temporary storage"; return KAIJU_GPU_ERR_ARG; }
+    if (sort_temp<P>(m, end_bit) > temp_bytes || scan_items_temp<P>(m) > temp_bytes || scan_flags_temp<P>(m) > temp_bytes) { err = "internal: suffix sort on the device: temporary storage"; return KAIJU_GPU_ERR_ARG; }
     tb = temp_bytes;
     SS_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, kb, vb, (size_t)m, 0u, end_bit, st));
-    uint64_t *items = kb.alternate();
-    uint32_t *flags = vb.alternate();
-    k_ss_heads<<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(kb.current(), m, first, items);
+    if constexpr (wide) {
+      if (!first) {                                         // sorted by rank[p + h]; now, stable, by rank[p]
+        k_ss_round_keys_hi<<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(vb.current(), m, d_rank.as<uint64_t>(), tlen, kb.current());
+        SS_HIP(hipGetLastError());
+        tb = temp_bytes;
+        SS_HIP(rocprim::radix_sort_pairs(d_temp.p, tb, kb, vb, (size_t)m, 0u, end_bit, st));
+      }
+    }
+    // wide: 16-byte items from the lower of (free key buffer, active list) over both of them
+    Item *items = wide ? reinterpret_cast<Item *>(std::min(reinterpret_cast<uint8_t *>(kb.alternate()), reinterpret_cast<uint8_t *>(act)))
+                       : reinterpret_cast<Item *>(kb.alternate());
+    P *flags = vb.alternate();
+    k_ss_heads<P><<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(kb.current(), vb.current(), d_rank.as<P>(), m, first, h, tlen, items);
     SS_HIP(hipGetLastError());
     tb = temp_bytes;
-    SS_HIP(rocprim::inclusive_scan(d_temp.p, tb, items, items, (size_t)m, SsScanMax(), st));
-    k_ss_ranks<<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(kb.current(), vb.current(), items, m, first, (uint32_t)nseq, tlen, d_rank.as<uint32_t>(), flags);
+    SS_HIP(rocprim::inclusive_scan(d_temp.p, tb, items, items, (size_t)m, typename SsTypes<P>::Scan(), st));
+    k_ss_ranks<P><<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(kb.current(), vb.current(), items, m, first, first_rank, tlen, d_rank.as<P>(), flags);
     SS_HIP(hipGetLastError());
     tb = temp_bytes;
-    SS_HIP(rocprim::inclusive_scan(d_temp.p, tb, flags, flags, (size_t)m, rocprim::plus<uint32_t>(), st));
-    k_ss_compact<<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(vb.current(), flags, m, d_act.as<uint32_t>());
+    SS_HIP(rocprim::inclusive_scan(d_temp.p, tb, flags, flags, (size_t)m, rocprim::plus<P>(), st));
+    k_ss_compact<P><<<grid_for(m), KJ_SS_BLOCK, 0, st>>>(vb.current(), flags, m, act);
     SS_HIP(hipGetLastError());
-    uint32_t left = 0;
-    SS_HIP(hipMemcpyAsync(&left, flags + (m - 1), 4, hipMemcpyDeviceToHost, st));
+    P left = 0;
+    SS_HIP(hipMemcpyAsync(&left, flags + (m - 1), sizeof(P), hipMemcpyDeviceToHost, st));
     SS_HIP(hipStreamSynchronize(st));                       // the one synchronisation of a round: is there another one?
     rounds++;
     h = first ? (uint64_t)KJ_SS_K : 2 * h;
@@ -313,9 +408,9 @@ int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, ui
     m = left;
     if (m == 0) break;
   }
-  k_ss_scatter<<<grid_for(nlanes), KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), d_rank.as<uint4>(), nlanes, (uint32_t)nseq, nsuf, d_v0.as<uint32_t>());
+  k_ss_scatter<P><<<grid_for(nlanes), KJ_SS_BLOCK, 0, st>>>(d_text.as<uint4>(), d_rank.as<P>(), nlanes, first_rank, nsuf, v0);
   SS_HIP(hipGetLastError());
-  if (!keep) SS_HIP(hipMemcpyAsync(sa_out, d_v0.p, 4 * nsuf, hipMemcpyDeviceToHost, st));
+  if (!keep) SS_HIP(hipMemcpyAsync(sa_out, v0, sizeof(P) * nsuf, hipMemcpyDeviceToHost, st));
   SS_HIP(hipEventRecord(ev.b, st));
   SS_HIP(hipStreamSynchronize(st));
   float ms = 0.f;
@@ -327,4 +422,33 @@ int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, ui
     keep->temp_bytes = temp_bytes; keep->nseq = nseq; keep->nsuf = nsuf; keep->maxlen = maxlen; keep->bytes = need;
   }
   return KAIJU_GPU_OK;
+}
+
+}  // namespace
+
+int kj_sufsort_check_device(int device_id, std::string &err) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { err = "suffix sort on the device: no HIP device (kaiju_build_fmi is the host builder)"; return KAIJU_GPU_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= n) { err = "suffix sort on the device: device_id " + std::to_string(device_id) + " of " + std::to_string(n) + " devices"; return KAIJU_GPU_ERR_ARG; }
+  return KAIJU_GPU_OK;
+}
+
+int kj_sufsort_device(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                      std::string &err) {
+  return sufsort_run<uint32_t>(text, tlen, device_id, sa_out, n_out, stats, nullptr, 0, err);
+}
+
+int kj_sufsort_device_keep(const uint8_t *text, uint64_t tlen, int device_id, uint32_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                           SsKeep *keep, std::string &err) {
+  return sufsort_run<uint32_t>(text, tlen, device_id, sa_out, n_out, stats, keep, 0, err);
+}
+
+int kj_sufsort_device_wide(const uint8_t *text, uint64_t tlen, int device_id, uint64_t *sa_out, uint64_t *n_out, kaiju_sufsort_stats *stats,
+                           uint64_t rank_bias, std::string &err) {
+  return sufsort_run<uint64_t>(text, tlen, device_id, sa_out, n_out, stats, nullptr, rank_bias, err);
+}
+
+uint64_t kj_sufsort_need_bytes(uint64_t tlen, uint64_t nsuf, uint64_t *temp_bytes_out) { return need_bytes<uint32_t>(tlen, nsuf, 0, temp_bytes_out); }
+uint64_t kj_sufsort_need_bytes_wide(uint64_t tlen, uint64_t nsuf, uint64_t rank_bias, uint64_t *temp_bytes_out) {
+  return need_bytes<uint64_t>(tlen, nsuf, rank_bias, temp_bytes_out);
 }

@@ -6,7 +6,8 @@ Test / benchmark infrastructure (csrc/mkfmi.h): a library of its own, kaiju_amd/
 C-ABI - the GPU box has no network and no reference binaries, bench.py and the tests make their indexes with it.
 
 ``device=<n>`` sorts the suffixes on that GPU (csrc/kj_sufsort.h) and writes the same bytes; it loads a third library,
-kaiju_amd/libkaiju_mkfmi_gpu.so.  With ``device=None`` (the default) that library is not touched.  ``stages="device"`` (with a
+kaiju_amd/libkaiju_mkfmi_gpu.so.  A file of 0xf0000000 bytes and more is sorted there with 64-bit positions (the wide instantiation
+of the same sort), a smaller one with 32-bit positions; ``stages="device"`` is for the smaller ones.  With ``device=None`` (the default) that library is not touched.  ``stages="device"`` (with a
 device; the default is ``"host"``) also runs the stages behind the sort there (csrc/kj_fmibuild.h): BWT, sequence ranks,
 replication, samples, checkpoints and byte coding; the same bytes again.  ``fmi_arrays`` gives those arrays for a text without
 writing a file, from the host stages or the device's."""
@@ -78,6 +79,7 @@ def _lib_gpu():
         L.kaiju_build_fmi_device.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
         L.kaiju_build_fmi_replicated_device.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int]
         L.kaiju_suffix_sort_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(SufsortStats)]
+        L.kaiju_suffix_sort_device_wide.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(SufsortStats), C.c_uint64]
         L.kaiju_build_fmi_device_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                                 C.POINTER(FmiBuildStats)]
         L.kaiju_fmi_arrays_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(FmiArrays), C.POINTER(FmiBuildStats)]
@@ -86,18 +88,25 @@ def _lib_gpu():
     return _LIB_GPU
 
 
-def suffix_sort(text, device: int = 0):
+def suffix_sort(text, device: int = 0, wide: bool = False, rank_bias: int = 0):
     """the suffix array of a text (uint8 codes 0 .. 20, a terminator 0 behind every sequence) sorted on a GPU: (sa, stats) with
     sa the positions of the letters in suffix order (uint32) and stats = {"rounds", "active": suffixes not final in front of
-    each of the first 16 rounds, "ms_sort"}"""
+    each of the first 16 rounds, "ms_sort"}.  wide: the instantiation of the sort with 64-bit positions (the one texts of
+    0xf0000000 symbols and more take); sa is uint64 then.  rank_bias (wide only, a test hook): every rank inside the sort is that
+    much higher, the result is the same."""
     import numpy as np
+    if rank_bias and not wide:
+        raise ValueError("rank_bias needs wide=True")
     L = _lib_gpu()
     t = np.ascontiguousarray(text, dtype=np.uint8)
-    sa = np.empty(max(1, int(np.count_nonzero(t))), dtype=np.uint32)
+    sa = np.empty(max(1, int(np.count_nonzero(t))), dtype=np.uint64 if wide else np.uint32)
     n, st = C.c_uint64(0), SufsortStats()
-    rc = L.kaiju_suffix_sort_device(t.ctypes.data, len(t), int(device), sa.ctypes.data, C.byref(n), C.byref(st))
+    if wide:
+        rc = L.kaiju_suffix_sort_device_wide(t.ctypes.data, len(t), int(device), sa.ctypes.data, C.byref(n), C.byref(st), int(rank_bias))
+    else:
+        rc = L.kaiju_suffix_sort_device(t.ctypes.data, len(t), int(device), sa.ctypes.data, C.byref(n), C.byref(st))
     if rc != 0:
-        raise api.KaijuGpuError(f"kaiju_suffix_sort_device failed ({rc}): {L.kaiju_build_fmi_error().decode()}")
+        raise api.KaijuGpuError(f"kaiju_suffix_sort_device{'_wide' if wide else ''} failed ({rc}): {L.kaiju_build_fmi_error().decode()}")
     return sa[: n.value], {"rounds": int(st.rounds), "active": [int(a) for a in st.active], "ms_sort": float(st.ms_sort)}
 
 
